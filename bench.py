@@ -14,6 +14,13 @@ Launch (driver contract):
   python bench.py --gpus 1 --steps 30 --warmup 10
   python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 \
       --master-addr 127.0.0.1 bench.py --gpus 8 --steps 30 --warmup 10
+
+A plain run sets up, warms up, times --steps steps and prints one JSON
+line. --dump-outputs DIR also writes one step's results as .npy files,
+computed by the timed path after the timed steps from the seeded initial
+state (same arguments => same inputs and, to rounding, same outputs, so
+two builds can be compared output for output). --full is where
+measurements beyond the headline figure belong; there are none today.
 """
 
 import argparse
@@ -35,6 +42,35 @@ if os.path.exists(os.path.join(_here, "tuning", "tunableop0.csv")):
     os.environ.setdefault("PYTORCH_TUNABLEOP_VERBOSE", "0")
 
 import torch
+
+# --dump-outputs writes each flat array whole up to this many elements
+# (16 MB of fp32); larger models get a fixed, seeded sample of this size.
+DUMP_MAX_ELEMS = 4 * 1024 * 1024
+
+
+def dump_outputs(out_dir: str, loss, master: torch.Tensor,
+                 adam_m: torch.Tensor) -> None:
+    """Write one step's results as float32 .npy files: loss.npy (shape
+    [1]), params.npy (the fp32 master parameters after the step) and
+    adam_m.npy (AdamW's first moment after the step: 0.1 x the step's
+    gradient when the optimizer state was fresh). The sample indices depend
+    only on the parameter count, so two builds run with the same arguments
+    write element-for-element comparable files."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "loss.npy"),
+            loss.detach().float().reshape(1).cpu().numpy())
+    idx = None
+    if master.numel() > DUMP_MAX_ELEMS:
+        g = torch.Generator().manual_seed(20240521)
+        idx = torch.randint(0, master.numel(), (DUMP_MAX_ELEMS,),
+                            generator=g).sort().values.to(master.device)
+    for name, t in (("params", master), ("adam_m", adam_m)):
+        flat = t.detach().reshape(-1)
+        if idx is not None:
+            flat = flat[idx]
+        np.save(os.path.join(out_dir, name + ".npy"),
+                flat.float().cpu().numpy())
 
 
 def main() -> int:
@@ -62,6 +98,15 @@ def main() -> int:
                         "(default: the config's reference-faithful values "
                         "— GPT-2 trains with transformers pdrop 0.1; pass "
                         "0 for a dropout-free ablation)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, run the timed step once "
+                        "more from the seeded initial state and write "
+                        "its loss, the updated fp32 parameters and "
+                        "AdamW's first moment as DIR/<name>.npy")
+    p.add_argument("--full", action="store_true",
+                   help="also run the measurements and checks beyond the "
+                        "headline figure (none today: a plain run already "
+                        "does only set-up, warmup and the timed steps)")
     args = p.parse_args()
 
     from distributedtraining_amd.config import Config, ModelConfig
@@ -125,6 +170,8 @@ def main() -> int:
                   file=sys.stderr)
 
     node.sync_initial_base()
+    # --dump-outputs replays one step from this seeded start (see below)
+    init_master = fp.master.clone() if args.dump_outputs else None
 
     def sync():
         if use_gpu:
@@ -189,6 +236,33 @@ def main() -> int:
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
     elapsed = float(t.item())
 
+    final_train_loss = node.miner.average_loss()
+
+    if args.dump_outputs:
+        # The state the last timed step starts from is the end of a
+        # trajectory that is not reproducible on the GPU: the backward
+        # kernels accumulate with fp32 atomics, and AdamW (reset at every
+        # merge, so its first updates are +-lr by the gradient's sign)
+        # amplifies the reordered sums. Two runs of one build, 25 steps of
+        # gpt2-small, ended 7e-3 apart per parameter and 8e-3 in the loss.
+        # One step from a fixed state is reproducible to rounding, so the
+        # dump is that: reinstall the seeded initial parameters, fresh
+        # optimizer state, the initial dropout counter, and run the timed
+        # path's step (graph replay or eager, whichever was timed) once
+        # more on the first pooled batch.
+        from distributedtraining_amd.ops import droprng
+        node.miner.install_base(init_master)
+        droprng.counter(fp.device).fill_(rank << 32)
+        if graphed is not None:
+            graphed.step(pool[0])
+            last_loss = graphed.loss
+        else:
+            last_loss = node.miner.train_step(pool[0])
+        sync()
+        if rank == 0:
+            dump_outputs(args.dump_outputs, last_loss, fp.master,
+                         node.miner.opt.m)
+
     tokens = args.steps * args.batch_size * args.seq_len * world
     value = tokens / elapsed
     if rank == 0:
@@ -215,7 +289,7 @@ def main() -> int:
                 "merge_strategy": args.merge_strategy,
                 "pdrop": cfg.model.resid_pdrop,
                 "optimizer": "fused AdamW (lr 5e-4, reference config)",
-                "final_train_loss": node.miner.average_loss(),
+                "final_train_loss": final_train_loss,
             },
         }
         print(json.dumps(out))

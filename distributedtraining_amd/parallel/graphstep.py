@@ -65,7 +65,8 @@ class GraphedMinerStep:
         sc, te = miner.step_count, miner.total_examples
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):
-            miner.train_step(self._static)
+            # static output: every replay rewrites it with that step's loss
+            self.loss = miner.train_step(self._static)
         miner.step_count, miner.total_examples = sc, te
         self.batch_size = int(self.ids.shape[0])
 

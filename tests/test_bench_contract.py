@@ -40,3 +40,33 @@ def test_single_process_bench_json():
     d = json.loads([ln for ln in r.stdout.splitlines()
                     if ln.startswith("{")][0])
     assert d["n_gpus"] == 1
+
+
+def test_dump_outputs_reproducible(tmp_path):
+    """--dump-outputs writes one replayed step's loss, parameters and AdamW
+    first moment as float32 .npy; the same arguments give the same inputs,
+    hence (on the deterministic CPU path) the same files, and --full is
+    accepted."""
+    import numpy as np
+    runs = []
+    for name, extra in (("a", []), ("b", ["--full"])):
+        out = tmp_path / name
+        r = subprocess.run(
+            [sys.executable, "bench.py", "--cpu", "--steps", "2",
+             "--warmup", "1", "--dump-outputs", str(out)] + extra,
+            cwd=REPO, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-2000:]
+        d = json.loads([ln for ln in r.stdout.splitlines()
+                        if ln.startswith("{")][0])
+        assert d["steps"] == 2 and d["ms_per_step"] > 0
+        arrs = {f.stem: np.load(f) for f in sorted(out.iterdir())}
+        assert set(arrs) == {"loss", "params", "adam_m"}
+        for a in arrs.values():
+            assert a.dtype == np.float32 and np.isfinite(a).all()
+        assert arrs["loss"].shape == (1,) and arrs["params"].ndim == 1
+        assert arrs["adam_m"].shape == arrs["params"].shape
+        assert np.abs(arrs["adam_m"]).max() > 0
+        assert sum(a.nbytes for a in arrs.values()) <= 64 * 2**20
+        runs.append(arrs)
+    for k in runs[0]:
+        np.testing.assert_array_equal(runs[0][k], runs[1][k])
