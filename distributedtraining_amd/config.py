@@ -113,6 +113,9 @@ class ValidateConfig:
     score_ema_alpha: float = 0.333333  # reference: btt_connector.py:317
     epoch_length: int = 100      # blocks between weight sets (base_subnet_config.py:72-77)
     outlier_threshold: float = 2.0     # MAD anomaly (btt_connector.py:387-426)
+    # score through ops.lm_head_loss (fused MFMA head + online CE, no
+    # logits tensor per eval batch); opt-in, see docs/architecture.md
+    fused_head_loss: bool = False
 
 
 @dataclass

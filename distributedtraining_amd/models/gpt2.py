@@ -124,7 +124,8 @@ class GPT2LM(nn.Module):
     def forward(self, input_ids: torch.Tensor,
                 attention_mask: Optional[torch.Tensor] = None,
                 labels: Optional[torch.Tensor] = None,
-                return_logits: Optional[bool] = None) -> CausalLMOutput:
+                return_logits: Optional[bool] = None,
+                loss_only: bool = False) -> CausalLMOutput:
         """``attention_mask`` ([B,S] of 1/0, right-padded — the reference's
         collate, neurons/miner.py:95-99): padded keys are masked out of
         attention AND padded label positions are ignored in the loss
@@ -157,6 +158,17 @@ class GPT2LM(nn.Module):
         if attention_mask is not None:
             tgt = tgt.masked_fill(attention_mask[:, 1:] == 0, -100)
         B, S = input_ids.shape
+        if loss_only:
+            # no-grad consumers (validator scoring): fused MFMA head + online
+            # CE, the [T, V] logits are never materialized
+            if self.training and torch.is_grad_enabled():
+                raise RuntimeError(
+                    "loss_only=True is forward-only: call it in eval mode or "
+                    "under torch.no_grad() (training needs the logits for "
+                    "backward)")
+            loss = ops.lm_head_loss(x[:, :-1, :], self.wte,
+                                    tgt.contiguous().view(-1))
+            return CausalLMOutput(loss=loss, logits=None)
         want_logits = bool(return_logits) or not self.training
         loss, logits = ops.lm_head_ce(x[:, :-1, :].contiguous(), self.wte,
                                       tgt.contiguous().view(-1),

@@ -134,7 +134,8 @@ class LlamaLM(nn.Module):
     def forward(self, input_ids: torch.Tensor,
                 attention_mask: Optional[torch.Tensor] = None,
                 labels: Optional[torch.Tensor] = None,
-                return_logits: Optional[bool] = None) -> CausalLMOutput:
+                return_logits: Optional[bool] = None,
+                loss_only: bool = False) -> CausalLMOutput:
         S = input_ids.shape[1]
         cos = self.rope_cos[:S]
         sin = self.rope_sin[:S]
@@ -156,6 +157,17 @@ class LlamaLM(nn.Module):
         if attention_mask is not None:   # pad targets ignored (-100)
             tgt = tgt.masked_fill(attention_mask[:, 1:] == 0, -100)
         B = input_ids.shape[0]
+        if loss_only:
+            # no-grad consumers (validator scoring): fused MFMA head + online
+            # CE, the [T, V] logits are never materialized
+            if self.training and torch.is_grad_enabled():
+                raise RuntimeError(
+                    "loss_only=True is forward-only: call it in eval mode or "
+                    "under torch.no_grad() (training needs the logits for "
+                    "backward)")
+            loss = ops.lm_head_loss(x[:, :-1, :], self._head(),
+                                    tgt.contiguous().view(-1))
+            return CausalLMOutput(loss=loss, logits=None)
         want_logits = bool(return_logits) or not self.training
         loss, logits = ops.lm_head_ce(x[:, :-1, :].contiguous(),
                                       self._head(),

@@ -33,7 +33,7 @@ __all__ = [
     "layer_norm", "rms_norm", "gelu", "swiglu", "causal_attention",
     "qkv_attention", "linear", "mlp_gelu", "add_layer_norm",
     "add_rms_norm",
-    "cross_entropy_loss", "lm_head_ce",
+    "cross_entropy_loss", "lm_head_ce", "lm_head_loss",
     "embedding_fwd",
     "decode_attention", "rope", "adamw_step", "delta_sub", "axpy_",
     "weighted_merge",
@@ -898,6 +898,69 @@ def lm_head_ce(x: torch.Tensor, w: torch.Tensor, targets: torch.Tensor,
     loss = F.cross_entropy(logits.float(), targets,
                            ignore_index=ignore_index)
     return loss, logits
+
+
+# --------------------------------------------------------------------------
+# Fused LM-head LOSS, forward only (hip/head_loss.hip): a hand-written MFMA
+# head GEMM whose accumulator tiles are folded into an online log-sum-exp
+# in-register — the [T, V] logits are never written. For the no-grad
+# consumers (validator scoring, cached base loss, sharded validation) that
+# throw the logits away; training keeps lm_head_ce, whose backward re-reads
+# them. Measured A/B: tools/head_loss_ab.py, profiles/r03_head_loss_ab.md.
+# --------------------------------------------------------------------------
+def _head_loss_supported(x2: torch.Tensor, w: torch.Tensor) -> bool:
+    """Shapes head_loss.hip takes: bf16, K % 64 == 0, dense 16 B-aligned
+    rows. Anything else keeps the library-GEMM + ce_fwd split."""
+    return (x2.dtype == torch.bfloat16 and w.dtype == torch.bfloat16
+            and w.dim() == 2 and x2.shape[-1] % 64 == 0
+            and w.is_contiguous()
+            and x2.data_ptr() % 16 == 0 and w.data_ptr() % 16 == 0)
+
+
+def lm_head_loss(x: torch.Tensor, w: torch.Tensor, targets: torch.Tensor,
+                 ignore_index: int = -100, return_lse: bool = False):
+    """Mean CE of ``x @ wᵀ`` against ``targets`` over non-ignored targets,
+    WITHOUT materializing the logits. x [..., K] is flattened to [T, K],
+    w is [V, K], targets has T elements. Returns a detached device scalar
+    (0.0 when every target is ignored), or ``(loss, lse)`` with the per-row
+    natural-log lse [T] (fp32) when ``return_lse`` is set.
+
+    Forward-only: this is not an autograd node. Asking for it with grad
+    enabled on inputs that require grad is an error — use ``lm_head_ce``.
+    Sync-free and hipGraph-capturable on GPU."""
+    if torch.is_grad_enabled() and (x.requires_grad or w.requires_grad):
+        raise RuntimeError(
+            "ops.lm_head_loss is forward-only (it keeps no logits for a "
+            "backward pass); call it under torch.no_grad(), or use "
+            "ops.lm_head_ce for a differentiable head + loss")
+    with torch.no_grad():
+        x2 = x.detach().reshape(-1, x.shape[-1])
+        w = w.detach()
+        tg = targets.reshape(-1)
+        if use_hip(x2):
+            m = require_ext()
+            if not x2.is_contiguous():
+                x2 = x2.contiguous()
+            if not tg.is_contiguous():
+                tg = tg.contiguous()
+            if not _head_loss_supported(x2, w):
+                # library GEMM + our CE kernel, the same split `linear`
+                # makes for GEMV
+                loss, logits = lm_head_ce(x2, w, tg, ignore_index)
+                if not return_lse:
+                    return loss
+                return loss, m.ce_fwd(logits, tg, ignore_index)[1]
+            loss_sum, lse, count, _tl = m.head_loss_fwd(x2, w, tg,
+                                                        ignore_index, 0)
+            loss = loss_sum / count.clamp(min=1).to(torch.float32)
+            return (loss, lse) if return_lse else loss
+        logits = F.linear(x2.float(), w.float())
+        valid = tg != ignore_index
+        lse = torch.logsumexp(logits, dim=-1)
+        tl = logits.gather(1, tg.clamp(min=0).unsqueeze(1)).squeeze(1)
+        loss = (torch.where(valid, lse - tl, torch.zeros_like(lse)).sum()
+                / valid.sum().clamp(min=1).to(torch.float32))
+        return (loss, lse) if return_lse else loss
 
 
 # --------------------------------------------------------------------------

@@ -3,6 +3,7 @@
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 
+#include <algorithm>
 #include <cmath>
 #include <vector>
 
@@ -400,6 +401,62 @@ std::vector<Tensor> ce_finalize(Tensor targets, Tensor m_run, Tensor s_run,
   return {loss.squeeze(0), lse, count.squeeze(0)};
 }
 
+// ---- fused LM-head loss (forward only) -------------------------------------
+// x2 [T,K] @ w[V,K]^T folded into per-row lse / target logit with no [T,V]
+// logits in memory. nsplit == 0: automatic vocab split from the CU count;
+// an explicit value is clamped to the number of vocab tiles. Returns
+// [loss_sum, lse (natural log), count, tlogit] as ce_fwd does.
+std::vector<Tensor> head_loss_fwd(Tensor x2, Tensor w, Tensor targets,
+                                  int64_t ignore_index, int64_t nsplit) {
+  check_bf16(x2, "x");
+  check_bf16(w, "w");
+  TORCH_CHECK(x2.dim() == 2 && w.dim() == 2, "x must be [T,K], w [V,K]");
+  const int64_t T = x2.size(0), K = x2.size(1), V = w.size(0);
+  TORCH_CHECK(w.size(1) == K, "x and w disagree on K");
+  TORCH_CHECK(K > 0 && K % 64 == 0 && K < (int64_t(1) << 31),
+              "head_loss needs K % 64 == 0");
+  TORCH_CHECK(V > 0 && V < (int64_t(1) << 31) - DTA_HEAD_LOSS_TILE,
+              "head_loss: bad vocab size");
+  TORCH_CHECK(T < (int64_t(1) << 31), "head_loss: too many rows");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(x2.data_ptr()) % 16 == 0 &&
+                  reinterpret_cast<uintptr_t>(w.data_ptr()) % 16 == 0,
+              "head_loss needs 16-byte aligned x and w");
+  TORCH_CHECK(targets.is_cuda() && targets.scalar_type() == torch::kInt64 &&
+                  targets.is_contiguous() && targets.dim() == 1 &&
+                  targets.numel() == T,
+              "targets must be a contiguous int64 [T] GPU tensor");
+  TORCH_CHECK(nsplit >= 0, "nsplit must be >= 0");
+  const auto f32 = x2.options().dtype(torch::kFloat32);
+  auto lse = torch::empty({T}, f32);
+  auto loss = torch::zeros({1}, f32);
+  auto count = torch::zeros({1}, f32.dtype(torch::kInt32));
+  auto tlogit = torch::zeros({T}, f32);
+  if (T == 0) return {loss.squeeze(0), lse, count.squeeze(0), tlogit};
+  const int64_t ntiles = (V + DTA_HEAD_LOSS_TILE - 1) / DTA_HEAD_LOSS_TILE;
+  int ns;
+  if (nsplit == 0) {
+    ns = dta_head_loss_nsplit(
+        T, V, at::cuda::getCurrentDeviceProperties()->multiProcessorCount);
+  } else {
+    ns = int(std::min<int64_t>(std::min<int64_t>(nsplit, ntiles), 65535));
+  }
+  auto ws = torch::empty({2, int64_t(ns), T}, f32);   // partial (m, s)
+  auto run = torch::empty({2, T}, f32);               // merged m_run, s_run
+  float* wsp = ws.data_ptr<float>();
+  float* rp = run.data_ptr<float>();
+  launch_head_loss(bfp(x2), bfp(w), targets.data_ptr<int64_t>(), T, V, int(K),
+                   ns, wsp, wsp + int64_t(ns) * T, tlogit.data_ptr<float>(),
+                   rp, rp + T, stream());
+  const hipError_t err = hipGetLastError();
+  TORCH_CHECK(err == hipSuccess, "head_loss launch failed: ",
+              hipGetErrorString(err));
+  launch_ce_finalize(targets.data_ptr<int64_t>(), rp, rp + T,
+                     tlogit.data_ptr<float>(), T, ignore_index,
+                     lse.data_ptr<float>(), loss.data_ptr<float>(),
+                     count.data_ptr<int>(), stream());
+  return {loss.squeeze(0), lse, count.squeeze(0), tlogit};
+}
+
 // scale_dev: empty tensor => host 'scale' scalar; else a 0/1-dim fp32
 // device scalar (dloss/count), keeping backward free of host syncs.
 // v0/nt: vocab-tile offset + store policy for the tiled pipeline.
@@ -756,6 +813,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("ce_bwd", &ce_bwd);
   m.def("ce_chunk", &ce_chunk);
   m.def("ce_finalize", &ce_finalize);
+  m.def("head_loss_fwd", &head_loss_fwd);
   m.def("embedding_fwd", &embedding_fwd);
   m.def("embedding_bwd", &embedding_bwd);
   m.def("kv_append", &kv_append);

@@ -163,6 +163,29 @@ void launch_ce_finalize(const int64_t* targets, const float* m_run,
                         int64_t rows, int64_t ignore_index, float* lse,
                         float* loss_sum, int* count, hipStream_t s);
 
+// ---- fused LM-head loss (forward only, no logits in memory) ----------------
+// MFMA head GEMM x[T,K] @ w[V,K]^T whose accumulator tiles are folded into
+// an online log-sum-exp in-register (head_loss.hip). K % 64 == 0, rows
+// 16 B aligned, T >= 1. grid = (ceil(T/tile), nsplit), 1 <= nsplit <= vocab
+// tiles; ws_m/ws_s: [nsplit, T] fp32 partials, folded in fixed order into
+// m_run/s_run (exp2 units, the launch_ce_finalize inputs); tlogit [T] must
+// be zeroed (only rows with an in-range target are written).
+constexpr int DTA_HEAD_LOSS_TILE = 128;
+// automatic vocab split: a few blocks per CU (2 are resident at 64 KB LDS),
+// every split owning at least one vocab tile
+inline int dta_head_loss_nsplit(int64_t T, int64_t V, int cus) {
+  const int64_t rb = (T + DTA_HEAD_LOSS_TILE - 1) / DTA_HEAD_LOSS_TILE;
+  const int64_t nt = (V + DTA_HEAD_LOSS_TILE - 1) / DTA_HEAD_LOSS_TILE;
+  int64_t ns = (4 * int64_t(cus) + rb - 1) / (rb > 0 ? rb : 1);
+  if (ns > nt) ns = nt;
+  if (ns > 65535) ns = 65535;  // gridDim.y
+  return int(ns < 1 ? 1 : ns);
+}
+void launch_head_loss(const bf16_t* x, const bf16_t* w,
+                      const int64_t* targets, int64_t T, int64_t V, int K,
+                      int nsplit, float* ws_m, float* ws_s, float* tlogit,
+                      float* m_run, float* s_run, hipStream_t s);
+
 // ---- embedding ------------------------------------------------------------
 // pos_p: device position offset for wpe (graph-replayable decode)
 void launch_embedding_fwd(const int64_t* ids, const bf16_t* wte,

@@ -55,13 +55,19 @@ class DeltaValidator:
     def evaluate_model(self) -> Tuple[float, float]:
         self.model.eval()
         total_loss, total_samples = 0.0, 0
+        # cfg.fused_head_loss: the LM families score through the fused
+        # no-logits head (ops.lm_head_loss). Passed only when set — the
+        # MLP/CNN families have no LM head and no such keyword.
+        head_kw = ({"loss_only": True}
+                   if getattr(self.cfg, "fused_head_loss", False) else {})
         for batch in self.eval_batches:
             ids = batch["input_ids"].to(self.fp.device)
             labels = batch.get("labels", batch["input_ids"]).to(self.fp.device)
             am = batch.get("attention_mask")
             if am is not None:
                 am = am.to(self.fp.device)
-            out = self.model(input_ids=ids, attention_mask=am, labels=labels)
+            out = self.model(input_ids=ids, attention_mask=am, labels=labels,
+                             **head_kw)
             total_loss += float(out.loss) * ids.shape[0]
             total_samples += ids.shape[0]
         self.model.train()
