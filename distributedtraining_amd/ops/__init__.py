@@ -222,7 +222,7 @@ def mlp_gelu(x: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor,
 
 
 # --------------------------------------------------------------------------
-# LayerNorm
+# LayerNorm / RMSNorm
 # --------------------------------------------------------------------------
 def _empty_like0(t):
     return t.new_empty(0)
@@ -242,40 +242,66 @@ def _grad_out(fp32_grad, main_grad, dtype):
     return fp32_grad.to(dtype)
 
 
-class _LayerNormFn(torch.autograd.Function):
+def _cpu_drop(t: torch.Tensor, p: float, site: int) -> torch.Tensor:
+    """Host gold of the counter-RNG dropout: t ⊙ mask / keep."""
+    keep = droprng.elem_keep_mask(t.numel(), droprng.value(t.device), site, p)
+    mask = torch.from_numpy(keep.astype("float32")).reshape(t.shape)
+    return t * (mask * droprng.inv_keep(p)).to(t.dtype)
+
+
+# The two norm Functions serve LayerNorm and RMSNorm: b is None => RMS.
+def _norm_fwd(x2, res, w, b, eps, site, p):
+    """-> (y, stats, sum); stats = (mean, rstd), or (rstd,) for RMS."""
+    m = require_ext()
+    if b is None:
+        y, rstd, s = m.rmsnorm_fwd(x2, res, w, eps, _rng0(x2), site, p)
+        return y, (rstd,), s
+    y, mean, rstd, s = m.layernorm_fwd(x2, res, w, b, eps, _rng0(x2), site, p)
+    return y, (mean, rstd), s
+
+
+def _norm_bwd(dy, ds, x2, w, stats, site, p):
+    """-> (dx, dw32, db32 or None, dres)."""
+    m = require_ext()
+    if len(stats) == 1:
+        dx, dw32, dres = m.rmsnorm_bwd(dy, ds, x2, w, *stats, _rng0(x2),
+                                       site, p)
+        return dx, dw32, None, dres
+    return m.layernorm_bwd(dy, ds, x2, w, *stats, _rng0(x2), site, p)
+
+
+class _NormFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, b, eps):
-        m = require_ext()
         x2 = x.contiguous()
-        y, mean, rstd, _ = m.layernorm_fwd(x2.view(-1, x2.shape[-1]),
-                                           _empty_like0(x2), w, b, eps,
-                                           _rng0(x), 0, 0.0)
-        ctx.save_for_backward(x2, w, mean, rstd)
+        y, stats, _ = _norm_fwd(x2.view(-1, x2.shape[-1]), _empty_like0(x2),
+                                w, b, eps, 0, 0.0)
+        ctx.save_for_backward(x2, w, *stats)
         ctx.wg = getattr(w, "main_grad", None)
         ctx.bg = getattr(b, "main_grad", None)
         return y.view_as(x2)
 
     @staticmethod
     def backward(ctx, dy):
-        m = require_ext()
-        x, w, mean, rstd = ctx.saved_tensors
+        x, w, *stats = ctx.saved_tensors
         N = x.shape[-1]
-        dx, dw32, db32, _ = m.layernorm_bwd(dy.contiguous().view(-1, N),
-                                            _empty_like0(x), x.view(-1, N),
-                                            w, mean, rstd, _rng0(x), 0, 0.0)
+        dx, dw32, db32, _ = _norm_bwd(dy.contiguous().view(-1, N),
+                                      _empty_like0(x), x.view(-1, N), w,
+                                      stats, 0, 0.0)
         return (dx.view_as(x), _grad_out(dw32, ctx.wg, w.dtype),
-                _grad_out(db32, ctx.bg, w.dtype), None)
+                None if db32 is None else _grad_out(db32, ctx.bg, w.dtype),
+                None)
 
 
 def layer_norm(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor,
                eps: float = 1e-5) -> torch.Tensor:
     if use_hip(x):
-        return _LayerNormFn.apply(x, w, b, eps)
+        return _NormFn.apply(x, w, b, eps)
     return F.layer_norm(x, (x.shape[-1],), w, b, eps)
 
 
-class _AddLayerNormFn(torch.autograd.Function):
-    """Fused residual-add + LayerNorm: (s, y) = (x+res, LN(x+res)).
+class _AddNormFn(torch.autograd.Function):
+    """Fused residual-add + norm: (s, y) = (x+res, norm(x+res)).
 
     The sum is rounded to bf16 before the statistics so backward (which
     recomputes the normalized values from the saved bf16 sum) matches
@@ -289,12 +315,10 @@ class _AddLayerNormFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, res, w, b, eps, p_drop, site):
-        m = require_ext()
         x2 = x.contiguous().view(-1, x.shape[-1])
         r2 = res.contiguous().view(-1, x.shape[-1])
-        y, mean, rstd, s = m.layernorm_fwd(x2, r2, w, b, eps, _rng0(x),
-                                           site, p_drop)
-        ctx.save_for_backward(s, w, mean, rstd)
+        y, stats, s = _norm_fwd(x2, r2, w, b, eps, site, p_drop)
+        ctx.save_for_backward(s, w, *stats)
         ctx.shape = x.shape
         ctx.drop = (p_drop, site)
         ctx.wg = getattr(w, "main_grad", None)
@@ -303,19 +327,18 @@ class _AddLayerNormFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, ds, dy):
-        m = require_ext()
-        s, w, mean, rstd = ctx.saved_tensors
+        s, w, *stats = ctx.saved_tensors
         p_drop, site = ctx.drop
         N = s.shape[-1]
         ds2 = (ds.contiguous().view(-1, N) if ds is not None
                else _empty_like0(s))
-        dx, dw32, db32, dres = m.layernorm_bwd(dy.contiguous().view(-1, N),
-                                               ds2, s, w, mean, rstd,
-                                               _rng0(s), site, p_drop)
+        dx, dw32, db32, dres = _norm_bwd(dy.contiguous().view(-1, N), ds2, s,
+                                         w, stats, site, p_drop)
         dx = dx.view(ctx.shape)
         dr = dres.view(ctx.shape) if p_drop > 0.0 else dx
         return (dx, dr, _grad_out(dw32, ctx.wg, w.dtype),
-                _grad_out(db32, ctx.bg, w.dtype), None, None, None)
+                None if db32 is None else _grad_out(db32, ctx.bg, w.dtype),
+                None, None, None)
 
 
 def add_layer_norm(x: torch.Tensor, res: torch.Tensor, w: torch.Tensor,
@@ -327,12 +350,9 @@ def add_layer_norm(x: torch.Tensor, res: torch.Tensor, w: torch.Tensor,
     (transformers resid_pdrop applied at the join that consumes the
     branch)."""
     if use_hip(x):
-        return _AddLayerNormFn.apply(x, res, w, b, eps, p_drop, site)
+        return _AddNormFn.apply(x, res, w, b, eps, p_drop, site)
     if p_drop > 0.0:
-        keep = droprng.elem_keep_mask(res.numel(),
-                                      droprng.value(x.device), site, p_drop)
-        mask = torch.from_numpy(keep.astype("float32")).reshape(res.shape)
-        res = res * (mask * droprng.inv_keep(p_drop)).to(res.dtype)
+        res = _cpu_drop(res, p_drop, site)
     s = x + res
     return s, F.layer_norm(s, (s.shape[-1],), w, b, eps)
 
@@ -340,72 +360,13 @@ def add_layer_norm(x: torch.Tensor, res: torch.Tensor, w: torch.Tensor,
 # --------------------------------------------------------------------------
 # RMSNorm (Llama family)
 # --------------------------------------------------------------------------
-class _RMSNormFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, w, eps):
-        m = require_ext()
-        x2 = x.contiguous()
-        y, rstd, _ = m.rmsnorm_fwd(x2.view(-1, x2.shape[-1]),
-                                   _empty_like0(x2), w, eps, _rng0(x), 0,
-                                   0.0)
-        ctx.save_for_backward(x2, w, rstd)
-        ctx.wg = getattr(w, "main_grad", None)
-        return y.view_as(x2)
-
-    @staticmethod
-    def backward(ctx, dy):
-        m = require_ext()
-        x, w, rstd = ctx.saved_tensors
-        N = x.shape[-1]
-        dx, dw32, _ = m.rmsnorm_bwd(dy.contiguous().view(-1, N),
-                                    _empty_like0(x), x.view(-1, N), w,
-                                    rstd, _rng0(x), 0, 0.0)
-        return dx.view_as(x), _grad_out(dw32, ctx.wg, w.dtype), None
-
-
-class _AddRMSNormFn(torch.autograd.Function):
-    """Fused residual-add + RMSNorm (the Llama-family twin of
-    _AddLayerNormFn): (s, y) = (x+drop(res), RMSNorm(...)); backward folds
-    the sum-stream gradient into dx and regenerates the dropout mask for
-    dres when p_drop > 0."""
-
-    @staticmethod
-    def forward(ctx, x, res, w, eps, p_drop, site):
-        m = require_ext()
-        x2 = x.contiguous().view(-1, x.shape[-1])
-        r2 = res.contiguous().view(-1, x.shape[-1])
-        y, rstd, s = m.rmsnorm_fwd(x2, r2, w, eps, _rng0(x), site, p_drop)
-        ctx.save_for_backward(s, w, rstd)
-        ctx.shape = x.shape
-        ctx.drop = (p_drop, site)
-        ctx.wg = getattr(w, "main_grad", None)
-        return s.view(x.shape), y.view(x.shape)
-
-    @staticmethod
-    def backward(ctx, ds, dy):
-        m = require_ext()
-        s, w, rstd = ctx.saved_tensors
-        p_drop, site = ctx.drop
-        N = s.shape[-1]
-        ds2 = (ds.contiguous().view(-1, N) if ds is not None
-               else _empty_like0(s))
-        dx, dw32, dres = m.rmsnorm_bwd(dy.contiguous().view(-1, N), ds2,
-                                       s, w, rstd, _rng0(s), site, p_drop)
-        dx = dx.view(ctx.shape)
-        dr = dres.view(ctx.shape) if p_drop > 0.0 else dx
-        return (dx, dr, _grad_out(dw32, ctx.wg, w.dtype), None, None, None)
-
-
 def add_rms_norm(x: torch.Tensor, res: torch.Tensor, w: torch.Tensor,
                  eps: float = 1e-5, p_drop: float = 0.0, site: int = 0):
     """(s, y) = (x + dropout(res), rms_norm(...))."""
     if use_hip(x):
-        return _AddRMSNormFn.apply(x, res, w, eps, p_drop, site)
+        return _AddNormFn.apply(x, res, w, None, eps, p_drop, site)
     if p_drop > 0.0:
-        keep = droprng.elem_keep_mask(res.numel(),
-                                      droprng.value(x.device), site, p_drop)
-        mask = torch.from_numpy(keep.astype("float32")).reshape(res.shape)
-        res = res * (mask * droprng.inv_keep(p_drop)).to(res.dtype)
+        res = _cpu_drop(res, p_drop, site)
     s = x + res
     sf = s.float()
     y = sf * torch.rsqrt(sf.pow(2).mean(-1, keepdim=True) + eps)
@@ -414,7 +375,7 @@ def add_rms_norm(x: torch.Tensor, res: torch.Tensor, w: torch.Tensor,
 
 def rms_norm(x: torch.Tensor, w: torch.Tensor, eps: float = 1e-5) -> torch.Tensor:
     if use_hip(x):
-        return _RMSNormFn.apply(x, w, eps)
+        return _NormFn.apply(x, w, None, eps)
     xf = x.float()
     y = xf * torch.rsqrt(xf.pow(2).mean(-1, keepdim=True) + eps)
     return (y * w.float()).to(x.dtype)
@@ -454,10 +415,7 @@ def dropout(x: torch.Tensor, p: float, site: int,
         return x
     if use_hip(x):
         return _DropoutFn.apply(x, site, p)
-    keep = droprng.elem_keep_mask(x.numel(), droprng.value(x.device),
-                                  site, p)
-    mask = torch.from_numpy(keep.astype("float32")).reshape(x.shape)
-    return x * (mask * droprng.inv_keep(p)).to(x.dtype)
+    return _cpu_drop(x, p, site)
 
 
 def rng_tick(device) -> None:

@@ -158,11 +158,11 @@ __global__ void attn_fwd_k(const ushort* __restrict__ q,
   const float sc2 = geo.scale * LOG2E;  // fold scale into the exp2 argument
   // padded batches: keys >= kvl are masked for every query (block-uniform)
   const int kvl = geo.kvlen ? min(seq, geo.kvlen[b]) : seq;
-  const uint32_t thr = geo.thr16;
+  const uint32_t thr = geo.drop.thr16;
   uint64_t drop_s2 = 0;
   if (thr)
-    drop_s2 = sm64(sm64(*geo.rng + geo.site * DTA_RNG_SITE_K) ^
-                   (uint64_t(bhid) * DTA_RNG_HEAD_K));
+    drop_s2 = rng_head_seed(rng_site_seed(geo.drop.rng, geo.drop.site),
+                            uint64_t(bhid));
 
   bf16x8 qb_[DTILES / 2];
   const int qrow = q0 + (lane & 15);
@@ -227,18 +227,15 @@ __global__ void attn_fwd_k(const ushort* __restrict__ q,
       // dropout on the PV accumulation only: l keeps the undropped sum,
       // so O = dropout(P) V with P the true softmax. One hash covers the
       // 4 consecutive keys this lane holds per half (k & 3 == r).
-      const uint64_t hq = drop_s2 + (uint64_t(uint32_t(qrow)) << 24) *
-                                        DTA_RNG_IDX_K;
+      const uint64_t hq = rng_attn_row(drop_s2, uint32_t(qrow));
       const uint64_t h0 =
-          sm64(hq + uint64_t(uint32_t((kv0 + 4 * g) >> 2)) * DTA_RNG_IDX_K);
-      const uint64_t h1 = sm64(
-          hq + uint64_t(uint32_t((kv0 + 16 + 4 * g) >> 2)) * DTA_RNG_IDX_K);
+          rng_attn_row_hash(hq, uint32_t((kv0 + 4 * g) >> 2));
+      const uint64_t h1 =
+          rng_attn_row_hash(hq, uint32_t((kv0 + 16 + 4 * g) >> 2));
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        p0[r] = (uint32_t(h0 >> (16 * r)) & 0xFFFF) >= thr
-                    ? p0[r] * geo.inv_keep : 0.f;
-        p1[r] = (uint32_t(h1 >> (16 * r)) & 0xFFFF) >= thr
-                    ? p1[r] * geo.inv_keep : 0.f;
+        p0[r] = rng_keep(h0, r, thr) ? p0[r] * geo.drop.inv_keep : 0.f;
+        p1[r] = rng_keep(h1, r, thr) ? p1[r] * geo.drop.inv_keep : 0.f;
       }
     }
     bf16x8 pa = scores_to_afrag(p0, p1, lane);
@@ -307,11 +304,11 @@ __global__ void attn_bwd_dq_k(const ushort* __restrict__ dout,
   const ushort* dop = dout + b * geo.db_ + h * geo.dh;
   const ushort* op2 = o + b * ob2 + h * oh2;
   const int kvl = geo.kvlen ? min(seq, geo.kvlen[b]) : seq;
-  const uint32_t thr = geo.thr16;
+  const uint32_t thr = geo.drop.thr16;
   uint64_t drop_s2 = 0;
   if (thr)
-    drop_s2 = sm64(sm64(*geo.rng + geo.site * DTA_RNG_SITE_K) ^
-                   (uint64_t(bhid) * DTA_RNG_HEAD_K));
+    drop_s2 = rng_head_seed(rng_site_seed(geo.drop.rng, geo.drop.site),
+                            uint64_t(bhid));
 
   const int qrow = q0 + (lane & 15);
   const int qr_ld = qrow < seq ? qrow : seq - 1;
@@ -370,11 +367,9 @@ __global__ void attn_bwd_dq_k(const ushort* __restrict__ dout,
     }
     uint64_t h0 = 0, h1 = 0;
     if (thr) {
-      const uint64_t hq =
-          drop_s2 + (uint64_t(uint32_t(qrow)) << 24) * DTA_RNG_IDX_K;
-      h0 = sm64(hq + uint64_t(uint32_t((kv0 + 4 * g) >> 2)) * DTA_RNG_IDX_K);
-      h1 = sm64(hq + uint64_t(uint32_t((kv0 + 16 + 4 * g) >> 2)) *
-                         DTA_RNG_IDX_K);
+      const uint64_t hq = rng_attn_row(drop_s2, uint32_t(qrow));
+      h0 = rng_attn_row_hash(hq, uint32_t((kv0 + 4 * g) >> 2));
+      h1 = rng_attn_row_hash(hq, uint32_t((kv0 + 16 + 4 * g) >> 2));
     }
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -387,10 +382,8 @@ __global__ void attn_bwd_dq_k(const ushort* __restrict__ dout,
       // dO·V term only; delta = rowsum(dO ⊙ O) already absorbs the mask
       float g0 = dp0[r], g1 = dp1[r];
       if (thr) {
-        g0 = (uint32_t(h0 >> (16 * r)) & 0xFFFF) >= thr
-                 ? g0 * geo.inv_keep : 0.f;
-        g1 = (uint32_t(h1 >> (16 * r)) & 0xFFFF) >= thr
-                 ? g1 * geo.inv_keep : 0.f;
+        g0 = rng_keep(h0, r, thr) ? g0 * geo.drop.inv_keep : 0.f;
+        g1 = rng_keep(h1, r, thr) ? g1 * geo.drop.inv_keep : 0.f;
       }
       s0[r] = P0 * (g0 - dlt_q);
       s1[r] = P1 * (g1 - dlt_q);
@@ -449,11 +442,11 @@ __global__ void attn_bwd_dkv_k(const ushort* __restrict__ dout,
   const ushort* dop = dout + b * geo.db_ + h * geo.dh;
   const float sc2 = geo.scale * LOG2E;
   const int kvl = geo.kvlen ? min(seq, geo.kvlen[b]) : seq;
-  const uint32_t thr = geo.thr16;
+  const uint32_t thr = geo.drop.thr16;
   uint64_t drop_s2 = 0;
   if (thr)
-    drop_s2 = sm64(sm64(*geo.rng + geo.site * DTA_RNG_SITE_K) ^
-                   (uint64_t(bhid) * DTA_RNG_HEAD_K));
+    drop_s2 = rng_head_seed(rng_site_seed(geo.drop.rng, geo.drop.site),
+                            uint64_t(bhid));
 
   const int krow = kv0 + (lane & 15);
   const int kr_ld = krow < seq ? krow : seq - 1;
@@ -520,16 +513,13 @@ __global__ void attn_bwd_dkv_k(const ushort* __restrict__ dout,
         // transposed view of the SAME per-(b,h,q,k) draw the fwd/dq
         // kernels take; dV uses the dropped P, dK the dropout-gated dS
         const uint64_t hk0 =
-            sm64(drop_s2 + ((uint64_t(uint32_t(qa0)) << 24) |
-                            uint64_t(uint32_t(krow) >> 2)) * DTA_RNG_IDX_K);
+            rng_attn_hash(drop_s2, uint32_t(qa0), uint32_t(krow) >> 2);
         const uint64_t hk1 =
-            sm64(drop_s2 + ((uint64_t(uint32_t(qa1)) << 24) |
-                            uint64_t(uint32_t(krow) >> 2)) * DTA_RNG_IDX_K);
-        const int sl = 16 * (krow & 3);
-        const float m0 = (uint32_t(hk0 >> sl) & 0xFFFF) >= thr
-                             ? geo.inv_keep : 0.f;
-        const float m1 = (uint32_t(hk1 >> sl) & 0xFFFF) >= thr
-                             ? geo.inv_keep : 0.f;
+            rng_attn_hash(drop_s2, uint32_t(qa1), uint32_t(krow) >> 2);
+        const float m0 =
+            rng_keep(hk0, krow & 3, thr) ? geo.drop.inv_keep : 0.f;
+        const float m1 =
+            rng_keep(hk1, krow & 3, thr) ? geo.drop.inv_keep : 0.f;
         // dS = A ⊙ (M/(1-p)·dp − delta); dV gets the dropped P = A·M/(1-p)
         ds0[r] = p0[r] * (m0 * dp0[r] - d0);
         ds1[r] = p1[r] * (m1 * dp1[r] - d1);

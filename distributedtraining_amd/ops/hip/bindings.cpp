@@ -4,7 +4,6 @@
 #include <ATen/hip/HIPContext.h>
 
 #include <algorithm>
-#include <cmath>
 #include <vector>
 
 #include "dta_kernels.h"
@@ -34,17 +33,11 @@ void check_f32(const Tensor& t, const char* name) {
   TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
 }
 
-// ---- norms ----------------------------------------------------------------
-// drop params shared by the norm bindings: p > 0 enables the fused
-// residual-branch dropout (counter RNG; thr16 quantization as elsewhere)
-struct DropArgs {
-  const unsigned long long* rng = nullptr;
-  unsigned long long site = 0;
-  unsigned int thr16 = 0;
-  float ik = 1.0f;
-};
-static DropArgs drop_args(const Tensor& rng, int64_t site, double p) {
-  DropArgs d;
+// ---- dropout parameters ----------------------------------------------------
+// p == 0 disables (defaults); else rng must be the int64 [1] device step
+// counter. The quantisation of p lives in dta_kernels.h.
+DropParams drop_params(const Tensor& rng, int64_t site, double p) {
+  DropParams d;
   if (p > 0.0) {
     TORCH_CHECK(p < 1.0, "dropout p must be < 1");
     TORCH_CHECK(rng.numel() == 1 && rng.scalar_type() == torch::kInt64 &&
@@ -52,124 +45,105 @@ static DropArgs drop_args(const Tensor& rng, int64_t site, double p) {
     d.rng = reinterpret_cast<const unsigned long long*>(
         rng.data_ptr<int64_t>());
     d.site = (unsigned long long)site;
-    unsigned int thr = (unsigned int)std::ceil(p * 65536.0);
-    if (thr > 65535u) thr = 65535u;
-    d.thr16 = thr;
-    d.ik = float(65536.0 / (65536.0 - double(thr)));
+    dta_drop_quantize(p, d);
   }
   return d;
 }
 
-// res: empty tensor => plain LN; else fused residual (returns the bf16
+// ---- norms ----------------------------------------------------------------
+// LayerNorm and RMSNorm share one implementation per direction; b == null
+// selects RMSNorm (no bias, no mean).
+int norm_cols(const Tensor& x, int max_cols, const char* what) {
+  check_bf16(x, "x");
+  TORCH_CHECK(x.size(1) % 8 == 0, "cols must be a multiple of 8");
+  TORCH_CHECK(x.size(1) <= max_cols, what, " supports cols <= ", max_cols,
+              " (register-resident row)");
+  return int(x.size(1));
+}
+
+// res: empty tensor => plain norm; else fused residual (returns the bf16
 // sum as an extra output feeding the ongoing residual stream). p > 0:
 // the branch is dropout-ed BEFORE the add (sum = x + drop(res)).
-std::vector<Tensor> layernorm_fwd(Tensor x, Tensor res, Tensor w, Tensor b,
-                                  double eps, Tensor rng, int64_t site,
-                                  double p) {
-  check_bf16(x, "x"); check_bf16(w, "w"); check_bf16(b, "b");
+// Returns {y, mean (undefined for RMS), rstd, sum}.
+std::vector<Tensor> norm_fwd(Tensor x, Tensor res, Tensor w, const Tensor* b,
+                             double eps, Tensor rng, int64_t site, double p) {
+  const int cols = norm_cols(x, DTA_NORM_FWD_MAX_COLS, "norm forward");
+  check_bf16(w, "w");
+  if (b) check_bf16(*b, "b");
   const int64_t rows = x.size(0);
-  const int cols = int(x.size(1));
-  TORCH_CHECK(cols % 8 == 0, "cols must be a multiple of 8");
-  TORCH_CHECK(cols <= 8192,
-              "norm kernels support cols <= 8192 (register-resident row)");
   const bool has_res = res.numel() > 0;
   if (has_res) check_bf16(res, "res");
   TORCH_CHECK(p == 0.0 || has_res, "dropout needs the residual branch");
-  const DropArgs da = drop_args(rng, site, p);
+  const DropParams drop = drop_params(rng, site, p);
+  const auto f32 = x.options().dtype(torch::kFloat32);
   auto y = torch::empty_like(x);
   auto sum = has_res ? torch::empty_like(x) : torch::empty({0}, x.options());
-  auto mean = torch::empty({rows}, x.options().dtype(torch::kFloat32));
-  auto rstd = torch::empty({rows}, x.options().dtype(torch::kFloat32));
-  launch_layernorm_fwd(bfp(x), has_res ? bfp(res) : nullptr,
-                       has_res ? bfp_mut(sum) : nullptr, bfp(w), bfp(b),
-                       bfp_mut(y), mean.data_ptr<float>(),
-                       rstd.data_ptr<float>(), rows, cols, float(eps),
-                       da.rng, da.site, da.thr16, da.ik, stream());
+  Tensor mean = b ? torch::empty({rows}, f32) : Tensor();
+  auto rstd = torch::empty({rows}, f32);
+  launch_norm_fwd({bfp(x), has_res ? bfp(res) : nullptr,
+                   has_res ? bfp_mut(sum) : nullptr, bfp(w),
+                   b ? bfp(*b) : nullptr, bfp_mut(y),
+                   b ? mean.data_ptr<float>() : nullptr,
+                   rstd.data_ptr<float>(), rows, cols, float(eps), drop, !b},
+                  stream());
   return {y, mean, rstd, sum};
 }
 
 // ds: empty tensor => plain; else the gradient arriving on the sum
-// stream, folded into dx (dx = ds + dLN/dx). p > 0: also emits
-// dres = dx ⊙ mask/(1-p) (4th output) for the dropped branch.
+// stream, folded into dx (dx = ds + dNorm/dx). p > 0: also emits
+// dres = dx ⊙ mask/(1-p) for the dropped branch.
+// Returns {dx, dw32, db32 (undefined for RMS), dres}; fp32 grads: the ops
+// layer accumulates or casts.
+std::vector<Tensor> norm_bwd(Tensor dy, Tensor ds, Tensor x, Tensor w,
+                             const Tensor* mean, Tensor rstd, Tensor rng,
+                             int64_t site, double p) {
+  const int cols = norm_cols(x, DTA_NORM_BWD_MAX_COLS, "norm backward");
+  check_bf16(dy, "dy"); check_bf16(w, "w");
+  const int64_t rows = x.size(0);
+  const bool has_ds = ds.numel() > 0;
+  if (has_ds) check_bf16(ds, "ds");
+  const DropParams drop = drop_params(rng, site, p);
+  auto dx = torch::empty_like(x);
+  auto dres = drop.thr16 ? torch::empty_like(x)
+                         : torch::empty({0}, x.options());
+  const auto f32 = x.options().dtype(torch::kFloat32);
+  auto dw32 = torch::zeros({cols}, f32);
+  Tensor db32 = mean ? torch::zeros({cols}, f32) : Tensor();
+  const int stripes = dta_norm_bwd_stripes(rows, cols);
+  auto part = torch::empty({mean ? 2 : 1, stripes, cols}, f32);
+  launch_norm_bwd({bfp(dy), has_ds ? bfp(ds) : nullptr, bfp(x), bfp(w),
+                   mean ? mean->data_ptr<float>() : nullptr,
+                   rstd.data_ptr<float>(), bfp_mut(dx),
+                   drop.thr16 ? bfp_mut(dres) : nullptr,
+                   dw32.data_ptr<float>(),
+                   mean ? db32.data_ptr<float>() : nullptr,
+                   part[0].data_ptr<float>(),
+                   mean ? part[1].data_ptr<float>() : nullptr, stripes, rows,
+                   cols, drop, !mean},
+                  stream());
+  return {dx, dw32, db32, dres};
+}
+
+std::vector<Tensor> layernorm_fwd(Tensor x, Tensor res, Tensor w, Tensor b,
+                                  double eps, Tensor rng, int64_t site,
+                                  double p) {
+  return norm_fwd(x, res, w, &b, eps, rng, site, p);
+}
 std::vector<Tensor> layernorm_bwd(Tensor dy, Tensor ds, Tensor x, Tensor w,
                                   Tensor mean, Tensor rstd, Tensor rng,
                                   int64_t site, double p) {
-  check_bf16(dy, "dy"); check_bf16(x, "x"); check_bf16(w, "w");
-  const int64_t rows = x.size(0);
-  const int cols = int(x.size(1));
-  TORCH_CHECK(cols % 8 == 0, "cols must be a multiple of 8");
-  TORCH_CHECK(cols <= 8192,
-              "norm kernels support cols <= 8192 (register-resident row)");
-  const bool has_ds = ds.numel() > 0;
-  if (has_ds) check_bf16(ds, "ds");
-  const DropArgs da = drop_args(rng, site, p);
-  auto dx = torch::empty_like(x);
-  auto dres = da.thr16 ? torch::empty_like(x)
-                       : torch::empty({0}, x.options());
-  auto f32 = x.options().dtype(torch::kFloat32);
-  auto dw32 = torch::zeros({cols}, f32);
-  auto db32 = torch::zeros({cols}, f32);
-  const int stripes = dta_norm_bwd_stripes(rows, cols);
-  auto part = torch::empty({2, stripes, cols}, f32);
-  launch_layernorm_bwd(bfp(dy), has_ds ? bfp(ds) : nullptr, bfp(x), bfp(w),
-                       mean.data_ptr<float>(), rstd.data_ptr<float>(),
-                       bfp_mut(dx), da.thr16 ? bfp_mut(dres) : nullptr,
-                       dw32.data_ptr<float>(), db32.data_ptr<float>(),
-                       part[0].data_ptr<float>(), part[1].data_ptr<float>(),
-                       stripes, rows, cols, da.rng, da.site, da.thr16,
-                       da.ik, stream());
-  return {dx, dw32, db32, dres};  // fp32 grads: ops layer accumulates or casts
+  return norm_bwd(dy, ds, x, w, &mean, rstd, rng, site, p);
 }
-
-std::vector<Tensor> rmsnorm_fwd(Tensor x, Tensor res, Tensor w,
-                                double eps, Tensor rng, int64_t site,
-                                double p) {
-  check_bf16(x, "x"); check_bf16(w, "w");
-  const int64_t rows = x.size(0);
-  const int cols = int(x.size(1));
-  TORCH_CHECK(cols % 8 == 0, "cols must be a multiple of 8");
-  TORCH_CHECK(cols <= 8192,
-              "norm kernels support cols <= 8192 (register-resident row)");
-  const bool has_res = res.numel() > 0;
-  if (has_res) check_bf16(res, "res");
-  TORCH_CHECK(p == 0.0 || has_res, "dropout needs the residual branch");
-  const DropArgs da = drop_args(rng, site, p);
-  auto y = torch::empty_like(x);
-  auto sum = has_res ? torch::empty_like(x) : torch::empty({0}, x.options());
-  auto rstd = torch::empty({rows}, x.options().dtype(torch::kFloat32));
-  launch_rmsnorm_fwd(bfp(x), has_res ? bfp(res) : nullptr,
-                     has_res ? bfp_mut(sum) : nullptr, bfp(w), bfp_mut(y),
-                     rstd.data_ptr<float>(), rows, cols, float(eps),
-                     da.rng, da.site, da.thr16, da.ik, stream());
-  return {y, rstd, sum};
+std::vector<Tensor> rmsnorm_fwd(Tensor x, Tensor res, Tensor w, double eps,
+                                Tensor rng, int64_t site, double p) {
+  auto o = norm_fwd(x, res, w, nullptr, eps, rng, site, p);
+  return {o[0], o[2], o[3]};  // y, rstd, sum
 }
-
 std::vector<Tensor> rmsnorm_bwd(Tensor dy, Tensor ds, Tensor x, Tensor w,
                                 Tensor rstd, Tensor rng, int64_t site,
                                 double p) {
-  check_bf16(dy, "dy"); check_bf16(x, "x"); check_bf16(w, "w");
-  const int64_t rows = x.size(0);
-  const int cols = int(x.size(1));
-  TORCH_CHECK(cols % 8 == 0, "cols must be a multiple of 8");
-  TORCH_CHECK(cols <= 8192,
-              "norm kernels support cols <= 8192 (register-resident row)");
-  const bool has_ds = ds.numel() > 0;
-  if (has_ds) check_bf16(ds, "ds");
-  const DropArgs da = drop_args(rng, site, p);
-  auto dx = torch::empty_like(x);
-  auto dres = da.thr16 ? torch::empty_like(x)
-                       : torch::empty({0}, x.options());
-  auto f32 = x.options().dtype(torch::kFloat32);
-  auto dw32 = torch::zeros({cols}, f32);
-  const int stripes = dta_norm_bwd_stripes(rows, cols);
-  auto part = torch::empty({stripes, cols}, f32);
-  launch_rmsnorm_bwd(bfp(dy), has_ds ? bfp(ds) : nullptr, bfp(x), bfp(w),
-                     rstd.data_ptr<float>(), bfp_mut(dx),
-                     da.thr16 ? bfp_mut(dres) : nullptr,
-                     dw32.data_ptr<float>(), part.data_ptr<float>(),
-                     stripes, rows, cols, da.rng, da.site, da.thr16, da.ik,
-                     stream());
-  return {dx, dw32, dres};  // fp32 grad
+  auto o = norm_bwd(dy, ds, x, w, nullptr, rstd, rng, site, p);
+  return {o[0], o[1], o[3]};  // dx, dw32, dres
 }
 
 // ---- elementwise ----------------------------------------------------------
@@ -208,16 +182,9 @@ Tensor swiglu_fwd(Tensor g, Tensor u) {
 Tensor dropout_apply(Tensor x, Tensor rng, int64_t site, double p) {
   check_bf16(x, "x");
   TORCH_CHECK(p > 0.0 && p < 1.0, "dropout p must be in (0,1)");
-  TORCH_CHECK(rng.numel() == 1 && rng.scalar_type() == torch::kInt64 &&
-                  rng.is_cuda(), "rng must be an int64 [1] GPU counter");
-  unsigned int thr = (unsigned int)std::ceil(p * 65536.0);
-  if (thr > 65535u) thr = 65535u;
-  const float inv_keep = float(65536.0 / (65536.0 - double(thr)));
+  const DropParams drop = drop_params(rng, site, p);
   auto y = torch::empty_like(x);
-  launch_dropout(bfp(x), bfp_mut(y), x.numel(),
-                 reinterpret_cast<const unsigned long long*>(
-                     rng.data_ptr<int64_t>()),
-                 (unsigned long long)site, thr, inv_keep, stream());
+  launch_dropout(bfp(x), bfp_mut(y), x.numel(), drop, stream());
   return y;
 }
 
@@ -603,8 +570,7 @@ static void check_attn_view(const Tensor& t, const char* n) {
 
 // kvlen: int32 [B] valid-key prefix per batch row (empty = no mask);
 // rng: int64 [1] device step counter + site/p: attention-prob dropout
-// (p == 0 disables). thr16 quantizes p to 1/65536 steps; inv_keep uses the
-// REALIZED keep probability so the expectation stays unbiased.
+// (p == 0 disables).
 static void set_mask_drop(AttnGeom& g, const Tensor& kvlen, const Tensor& rng,
                           int64_t site, double p, int64_t B) {
   if (kvlen.numel() > 0) {
@@ -613,19 +579,7 @@ static void set_mask_drop(AttnGeom& g, const Tensor& kvlen, const Tensor& rng,
                 "kvlen must be a contiguous int32 [B] GPU tensor");
     g.kvlen = kvlen.data_ptr<int>();
   }
-  if (p > 0.0) {
-    TORCH_CHECK(p < 1.0, "dropout p must be < 1");
-    TORCH_CHECK(rng.numel() == 1 && rng.scalar_type() == torch::kInt64 &&
-                    rng.is_cuda(),
-                "rng must be an int64 [1] GPU counter");
-    g.rng = reinterpret_cast<const unsigned long long*>(
-        rng.data_ptr<int64_t>());
-    g.site = (unsigned long long)site;
-    unsigned int thr = (unsigned int)std::ceil(p * 65536.0);
-    if (thr > 65535u) thr = 65535u;
-    g.thr16 = thr;
-    g.inv_keep = float(65536.0 / (65536.0 - double(thr)));
-  }
+  g.drop = drop_params(rng, site, p);
 }
 
 static AttnGeom make_geom(const Tensor& q, const Tensor& k, const Tensor& v,

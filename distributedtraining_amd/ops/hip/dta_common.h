@@ -121,6 +121,36 @@ DEV uint64_t sm64(uint64_t z) {
 #define DTA_RNG_SITE_K 0xA24BAED4963EE407ULL
 #define DTA_RNG_HEAD_K 0x9E3779B97F4A7C15ULL
 #define DTA_RNG_IDX_K 0xD1B54A32D192ED03ULL
+// The chain above, spelled once: kernels call these and never name a
+// constant, a shift or the 16-bit mask themselves.
+DEV uint64_t rng_site_seed(const unsigned long long* ctr,
+                           unsigned long long site) {   // s1
+  return sm64(*ctr + site * DTA_RNG_SITE_K);
+}
+DEV uint64_t rng_head_seed(uint64_t s1, uint64_t bh) {  // s2
+  return sm64(s1 ^ (bh * DTA_RNG_HEAD_K));
+}
+// elementwise hash of the 4 elements i with i >> 2 == quad
+DEV uint64_t rng_elem_hash(uint64_t s1, uint64_t quad) {
+  return sm64(s1 + quad * DTA_RNG_IDX_K);
+}
+// attention hash of query q and the 4 keys k with k >> 2 == kquad
+DEV uint64_t rng_attn_hash(uint64_t s2, uint32_t q, uint32_t kquad) {
+  return sm64(s2 + ((uint64_t(q) << 24) | uint64_t(kquad)) * DTA_RNG_IDX_K);
+}
+// the same hash split for kernels that walk keys per query row: the row
+// term is hoisted, each key quad costs one multiply-add. Equal to
+// rng_attn_hash mod 2^64 because kquad < 2^24 makes the | a +.
+DEV uint64_t rng_attn_row(uint64_t s2, uint32_t q) {
+  return s2 + (uint64_t(q) << 24) * DTA_RNG_IDX_K;
+}
+DEV uint64_t rng_attn_row_hash(uint64_t row, uint32_t kquad) {
+  return sm64(row + uint64_t(kquad) * DTA_RNG_IDX_K);
+}
+// keep-test of element slot (index & 3) of a hash
+DEV bool rng_keep(uint64_t h, int slot, uint32_t thr16) {
+  return (uint32_t(h >> (16 * slot)) & 0xFFFF) >= thr16;
+}
 
 // ---- grid sizing (Guideline 11: cap + grid-stride for memory-bound) -------
 constexpr int MAX_RESIDENT_BLOCKS = 2048;  // 256 CU x 8 blocks

@@ -3,10 +3,29 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <cmath>
 #include <cstdint>
 #include <cstdlib>
 
 using bf16_t = unsigned short;  // raw bf16 bits at the ABI boundary
+
+// ---- counter-RNG dropout parameters (chain: dta_common.h) ------------------
+// rng: device uint64 step counter; site: per-call-site salt; thr16 == 0
+// disables dropout.
+struct DropParams {
+  const unsigned long long* rng = nullptr;
+  unsigned long long site = 0;
+  unsigned int thr16 = 0;
+  float inv_keep = 1.0f;
+};
+// The one place p is quantised: thr16 = min(ceil(p * 2^16), 2^16 - 1) and
+// inv_keep is the reciprocal of the REALIZED keep probability, so the
+// expectation stays unbiased.
+inline void dta_drop_quantize(double p, DropParams& d) {
+  const double full = 65536.0;
+  d.thr16 = (unsigned int)std::fmin(std::ceil(p * full), full - 1.0);
+  d.inv_keep = float(full / (full - double(d.thr16)));
+}
 
 // ---- elementwise ----------------------------------------------------------
 void launch_gelu_fwd(const bf16_t* x, bf16_t* y, int64_t n, hipStream_t s);
@@ -22,8 +41,7 @@ void launch_swiglu_bwd(const bf16_t* dy, const bf16_t* g, const bf16_t* u,
 // counter-based dropout (fwd and bwd are the same masked scale; the mask
 // is regenerated, never stored). rng: device uint64 step counter.
 void launch_dropout(const bf16_t* x, bf16_t* y, int64_t n,
-                    const unsigned long long* rng, unsigned long long site,
-                    unsigned int thr16, float inv_keep, hipStream_t s);
+                    const DropParams& drop, hipStream_t s);
 void launch_rng_tick(unsigned long long* ctr, hipStream_t s);
 // dst (bf16 grad view) += src (fp32): replaces cast + autograd-add pairs
 void launch_accum_f32_bf16(bf16_t* dst, const float* src, int64_t n,
@@ -106,41 +124,47 @@ inline int dta_norm_bwd_stripes(int64_t rows, int cols) {
   return dta_norm_fused_dwdb(cols) ? dta_norm_bwd_grid(rows)
                                    : dta_colred_stripes(rows, cols);
 }
+// Row-width limits of the register-resident kernels: the forward is
+// instantiated up to 16 iterations of 64 lanes x 8 columns, the backward
+// up to 8 (a 16-iteration backward would hold 3*16*8 fp32 per lane).
+constexpr int DTA_NORM_FWD_MAX_COLS = 8192;
+constexpr int DTA_NORM_BWD_MAX_COLS = 4096;
+// One argument struct per direction, filled once in the bindings.
+// rms: RMSNorm instead of LayerNorm; b, mean, db and pdb are then null.
 // res/sum_out: optional fused residual (sum = bf16(x+res) feeds both the
 // statistics and the ongoing stream); ds: optional additive gradient on
 // the sum stream folded into dx.
-// rng/site/thr16/ik: counter-RNG dropout fused onto the incoming residual
-// branch (thr16 == 0 disables; requires res). Backward emits the branch
+// drop: counter-RNG dropout fused onto the incoming residual branch
+// (thr16 == 0 disables; requires res). Backward emits the branch
 // gradient dres = dx ⊙ mask/(1-p) when enabled.
-void launch_layernorm_fwd(const bf16_t* x, const bf16_t* res,
-                          bf16_t* sum_out, const bf16_t* w, const bf16_t* b,
-                          bf16_t* y, float* mean, float* rstd, int64_t rows,
-                          int cols, float eps, const unsigned long long* rng,
-                          unsigned long long site, unsigned int thr16,
-                          float ik, hipStream_t s);
-// pdw/pdb: [stripes, cols] fp32 workspaces (dta_colred_stripes rows); the
-// two-phase column reduction is atomic-free and deterministic.
-void launch_layernorm_bwd(const bf16_t* dy, const bf16_t* ds,
-                          const bf16_t* x, const bf16_t* w,
-                          const float* mean, const float* rstd, bf16_t* dx,
-                          bf16_t* dres, float* dw, float* db, float* pdw,
-                          float* pdb, int stripes, int64_t rows, int cols,
-                          const unsigned long long* rng,
-                          unsigned long long site, unsigned int thr16,
-                          float ik, hipStream_t s);
-void launch_rmsnorm_fwd(const bf16_t* x, const bf16_t* res,
-                        bf16_t* sum_out, const bf16_t* w, bf16_t* y,
-                        float* rstd, int64_t rows, int cols, float eps,
-                        const unsigned long long* rng,
-                        unsigned long long site, unsigned int thr16,
-                        float ik, hipStream_t s);
-void launch_rmsnorm_bwd(const bf16_t* dy, const bf16_t* ds,
-                        const bf16_t* x, const bf16_t* w,
-                        const float* rstd, bf16_t* dx, bf16_t* dres,
-                        float* dw, float* pdw, int stripes, int64_t rows,
-                        int cols, const unsigned long long* rng,
-                        unsigned long long site, unsigned int thr16,
-                        float ik, hipStream_t s);
+struct NormFwdArgs {
+  const bf16_t *x, *res;
+  bf16_t* sum_out;
+  const bf16_t *w, *b;
+  bf16_t* y;
+  float *mean, *rstd;
+  int64_t rows;
+  int cols;  // % 8 == 0, <= DTA_NORM_FWD_MAX_COLS
+  float eps;
+  DropParams drop;
+  bool rms;
+};
+// pdw/pdb: [stripes, cols] fp32 workspaces (dta_norm_bwd_stripes rows) of
+// the two-phase dγ/dβ column reduction; its second phase finishes with
+// atomicAdd into the pre-zeroed dw/db, so they do not repeat bit for bit.
+struct NormBwdArgs {
+  const bf16_t *dy, *ds, *x, *w;
+  const float *mean, *rstd;
+  bf16_t *dx, *dres;
+  float *dw, *db, *pdw, *pdb;
+  int stripes;
+  int64_t rows;
+  int cols;  // % 8 == 0, <= DTA_NORM_BWD_MAX_COLS
+  DropParams drop;
+  bool rms;
+};
+void launch_norm_fwd(const NormFwdArgs& a, hipStream_t s);
+void launch_norm_bwd(const NormBwdArgs& a, hipStream_t s);
 
 // ---- fused cross entropy --------------------------------------------------
 void launch_ce_fwd(const bf16_t* logits, const int64_t* targets,
@@ -230,12 +254,8 @@ struct AttnGeom {
   // training_manager.py:380-385): key j of batch row b is valid iff
   // j < kvlen[b]. null = no mask (all keys valid).
   const int* kvlen = nullptr;
-  // attention-probability dropout (transformers GPT-2 attn_pdrop):
-  // thr16 == 0 disables; rng = device step counter (dta_common.h RNG).
-  const unsigned long long* rng = nullptr;
-  unsigned long long site = 0;
-  unsigned int thr16 = 0;
-  float inv_keep = 1.0f;
+  // attention-probability dropout (transformers GPT-2 attn_pdrop)
+  DropParams drop;
 };
 void launch_attn_fwd(const bf16_t* q, const bf16_t* k, const bf16_t* v,
                      bf16_t* o, float* lse, const AttnGeom& geo,

@@ -13,6 +13,9 @@
 #include "dta_common.h"
 #include "dta_kernels.h"
 
+#include <cstdio>
+#include <type_traits>
+
 namespace {
 
 constexpr int ROW_WAVES = 4;
@@ -39,7 +42,7 @@ __global__ void norm_fwd_k(const ushort* __restrict__ x,
                            float inv_keep) {
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const int nchunk = cols >> 3;
-  const uint64_t s1d = DROP ? sm64(*rng + site * DTA_RNG_SITE_K) : 0;
+  const uint64_t s1d = DROP ? rng_site_seed(rng, site) : 0;
   for (int64_t row = int64_t(blockIdx.x) * ROW_WAVES + wid; row < rows;
        row += int64_t(gridDim.x) * ROW_WAVES) {
     const ushort* xr = x + row * cols;
@@ -57,8 +60,8 @@ __global__ void norm_fwd_k(const ushort* __restrict__ x,
         uint64_t h0 = 0, h1 = 0;
         if (DROP) {
           const int64_t i0 = row * cols + int64_t(c) * 8;
-          h0 = sm64(s1d + uint64_t(i0 >> 2) * DTA_RNG_IDX_K);
-          h1 = sm64(s1d + uint64_t((i0 >> 2) + 1) * DTA_RNG_IDX_K);
+          h0 = rng_elem_hash(s1d, uint64_t(i0 >> 2));
+          h1 = rng_elem_hash(s1d, uint64_t((i0 >> 2) + 1));
         }
         s16x8 vs;
 #pragma unroll
@@ -68,8 +71,7 @@ __global__ void norm_fwd_k(const ushort* __restrict__ x,
             float rf = bf2f(ushort(vr[j]));
             if (DROP) {
               const uint64_t h = (j < 4) ? h0 : h1;
-              rf = ((uint32_t(h >> (16 * (j & 3))) & 0xFFFF) >= thr16)
-                       ? rf * inv_keep : 0.f;
+              rf = rng_keep(h, j & 3, thr16) ? rf * inv_keep : 0.f;
             }
             const ushort sb = f2bf(f + rf);
             vs[j] = sb;
@@ -149,7 +151,7 @@ __global__ void norm_bwd_dx_k(const ushort* __restrict__ dy,
                               float inv_keep) {
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const int nchunk = cols >> 3;
-  const uint64_t s1d = DROP ? sm64(*rng + site * DTA_RNG_SITE_K) : 0;
+  const uint64_t s1d = DROP ? rng_site_seed(rng, site) : 0;
   float dwp[FDW ? ITERS : 1][8], dbp[(FDW && !RMS) ? ITERS : 1][8];
   if (FDW) {
 #pragma unroll
@@ -217,8 +219,8 @@ __global__ void norm_bwd_dx_k(const ushort* __restrict__ dy,
         uint64_t h0 = 0, h1 = 0;
         if (DROP) {
           const int64_t i0 = row * cols + int64_t(c) * 8;
-          h0 = sm64(s1d + uint64_t(i0 >> 2) * DTA_RNG_IDX_K);
-          h1 = sm64(s1d + uint64_t((i0 >> 2) + 1) * DTA_RNG_IDX_K);
+          h0 = rng_elem_hash(s1d, uint64_t(i0 >> 2));
+          h1 = rng_elem_hash(s1d, uint64_t((i0 >> 2) + 1));
         }
         s16x8 o, od;
 #pragma unroll
@@ -230,8 +232,8 @@ __global__ void norm_bwd_dx_k(const ushort* __restrict__ dy,
           o[j] = f2bf(g);
           if (DROP) {
             const uint64_t h = (j < 4) ? h0 : h1;
-            od[j] = ((uint32_t(h >> (16 * (j & 3))) & 0xFFFF) >= thr16)
-                        ? f2bf(g * inv_keep) : ushort(0);
+            od[j] = rng_keep(h, j & 3, thr16) ? f2bf(g * inv_keep)
+                                              : ushort(0);
           }
         }
         *reinterpret_cast<s16x8*>(dxr + c * 8) = o;
@@ -339,171 +341,81 @@ __global__ void dwdb_reduce_k(const float* __restrict__ pdw,
   }
 }
 
-template <bool RMS, bool RES, bool DROP>
-void dispatch_fwd(const ushort* x, const ushort* res, ushort* sum_out,
-                  const ushort* w, const ushort* b, ushort* y, float* mean,
-                  float* rstd, int64_t rows, int cols, float eps,
-                  const unsigned long long* rng, unsigned long long site,
-                  unsigned int thr16, float ik, hipStream_t s) {
-  const int nchunk = cols >> 3;
-  const int iters = (nchunk + 63) / 64;
-  int64_t want = (rows + ROW_WAVES - 1) / ROW_WAVES;
-  const int grid = int(want < 4096 ? (want > 0 ? want : 1) : 4096);
-  const dim3 blk(64 * ROW_WAVES);
-#define CASE_F(I)                                                         \
-  case I:                                                                 \
-    norm_fwd_k<I, RMS, RES, DROP><<<grid, blk, 0, s>>>(                   \
-        x, res, sum_out, w, b, y, mean, rstd, rows, cols, eps, rng, site, \
-        thr16, ik);                                                       \
-    break;
-  switch (iters) {
-    CASE_F(1) CASE_F(2) CASE_F(3) CASE_F(4) CASE_F(6) CASE_F(8) CASE_F(16)
-    default: {
-      if (iters <= 6) { norm_fwd_k<6, RMS, RES, DROP><<<grid, blk, 0, s>>>(x, res, sum_out, w, b, y, mean, rstd, rows, cols, eps, rng, site, thr16, ik); }
-      else if (iters <= 8) { norm_fwd_k<8, RMS, RES, DROP><<<grid, blk, 0, s>>>(x, res, sum_out, w, b, y, mean, rstd, rows, cols, eps, rng, site, thr16, ik); }
-      else { norm_fwd_k<16, RMS, RES, DROP><<<grid, blk, 0, s>>>(x, res, sum_out, w, b, y, mean, rstd, rows, cols, eps, rng, site, thr16, ik); }
-    }
+// ---- launch path ----------------------------------------------------------
+// The instantiated row widths, in iterations of 64 lanes x 8 columns, for
+// both directions (the backward stops at DTA_NORM_BWD_MAX_COLS). A row
+// runs on the smallest entry >= ceil(cols / 8 / 64). Rounding up is exact:
+// the iterations past the row's end are masked (c >= nchunk) and add
+// nothing to the sums, so every entry wide enough gives the same bits.
+constexpr int NORM_ITERS[] = {1, 2, 3, 4, 6, 8, 16};
+constexpr int N_NORM_ITERS = sizeof(NORM_ITERS) / sizeof(int);
+constexpr int ITER_COLS = WAVE * 8;  // columns one iteration covers
+static_assert(NORM_ITERS[N_NORM_ITERS - 1] * ITER_COLS == DTA_NORM_FWD_MAX_COLS &&
+              NORM_ITERS[N_NORM_ITERS - 2] * ITER_COLS == DTA_NORM_BWD_MAX_COLS);
+
+// f(integral_constant<ITERS>) for the table entry that fits cols <= MAXC
+template <int MAXC, int K = 0, class F>
+void with_iters(int cols, F&& f) {
+  if constexpr (K < N_NORM_ITERS && NORM_ITERS[K] * ITER_COLS <= MAXC) {
+    if (cols <= NORM_ITERS[K] * ITER_COLS)
+      f(std::integral_constant<int, NORM_ITERS[K]>{});
+    else
+      with_iters<MAXC, K + 1>(cols, f);
+  } else {
+    fprintf(stderr, "norm kernels: cols=%d beyond the limit %d\n", cols, MAXC);
+    abort();  // the bindings check the limit first
   }
-#undef CASE_F
 }
 
-template <bool RMS, bool DS, bool DROP>
-void dispatch_bwd(const ushort* dy, const ushort* ds, const ushort* x,
-                  const ushort* w, const float* mean, const float* rstd,
-                  ushort* dx, ushort* dres, float* dw, float* db, float* pdw,
-                  float* pdb, int stripes, int64_t rows, int cols,
-                  const unsigned long long* rng, unsigned long long site,
-                  unsigned int thr16, float ik, hipStream_t s) {
-  const int nchunk = cols >> 3;
-  const int iters = (nchunk + 63) / 64;
-  const bool fdw = dta_norm_fused_dwdb(cols);
-  const int grid = dta_norm_bwd_grid(rows);
-  const dim3 blk(64 * ROW_WAVES);
-#define CASE_B(I)                                                            \
-  case I:                                                                    \
-    if (fdw)                                                                 \
-      norm_bwd_dx_k<I, RMS, DS, DROP, true><<<grid, blk, 0, s>>>(            \
-          dy, ds, x, w, mean, rstd, dx, dres, pdw, pdb, rows, cols, rng,     \
-          site, thr16, ik);                                                  \
-    else                                                                     \
-      norm_bwd_dx_k<I, RMS, DS, DROP, false><<<grid, blk, 0, s>>>(           \
-          dy, ds, x, w, mean, rstd, dx, dres, nullptr, nullptr, rows, cols,  \
-          rng, site, thr16, ik);                                             \
-    break;
-  switch (iters) {
-    CASE_B(1) CASE_B(2) CASE_B(3) CASE_B(4) CASE_B(6) CASE_B(8)
-    default:
-      norm_bwd_dx_k<8, RMS, DS, DROP, false><<<grid, blk, 0, s>>>(
-          dy, ds, x, w, mean, rstd, dx, dres, nullptr, nullptr, rows, cols,
-          rng, site, thr16, ik);
-  }
-#undef CASE_B
-  if (!fdw) {
-    const ColRedCfg cfg = dta_colred_cfg(rows, cols);
-    dim3 g2(cfg.gx, unsigned(stripes));
-    norm_bwd_dwdb_part_k<RMS><<<g2, cfg.threads, 0, s>>>(
-        dy, x, mean, rstd, pdw, RMS ? nullptr : pdb, rows, cols);
-  }
-  const int g3 = (cols / 4 + 255) / 256;
-  // stripe-parallelism scales with the panel height (the fused path
-  // produces up to 4096 panel rows; 32 y-blocks left 128-deep serial
-  // loops on an underfilled chip)
-  const int ry = stripes < 32 ? stripes : (stripes > 1024 ? 256 : 32);
-  dwdb_reduce_k<<<dim3(g3, ry), 256, 0, s>>>(pdw, RMS ? nullptr : pdb, dw,
-                                             db, stripes, cols);
+// f(bool_constant...) with run-time flags turned into template arguments
+template <bool... Bs, class F>
+void with_flags(F&& f) { f(std::bool_constant<Bs>{}...); }
+template <bool... Bs, class F, class... Rest>
+void with_flags(F&& f, bool b, Rest... rest) {
+  b ? with_flags<Bs..., true>(f, rest...)
+    : with_flags<Bs..., false>(f, rest...);
 }
 
 }  // namespace
 
-void launch_layernorm_fwd(const bf16_t* x, const bf16_t* res,
-                          bf16_t* sum_out, const bf16_t* w, const bf16_t* b,
-                          bf16_t* y, float* mean, float* rstd, int64_t rows,
-                          int cols, float eps, const unsigned long long* rng,
-                          unsigned long long site, unsigned int thr16,
-                          float ik, hipStream_t s) {
-  if (res && thr16)
-    dispatch_fwd<false, true, true>(x, res, sum_out, w, b, y, mean, rstd,
-                                    rows, cols, eps, rng, site, thr16, ik,
-                                    s);
-  else if (res)
-    dispatch_fwd<false, true, false>(x, res, sum_out, w, b, y, mean, rstd,
-                                     rows, cols, eps, nullptr, 0, 0, 1.f,
-                                     s);
-  else
-    dispatch_fwd<false, false, false>(x, nullptr, nullptr, w, b, y, mean,
-                                      rstd, rows, cols, eps, nullptr, 0, 0,
-                                      1.f, s);
+void launch_norm_fwd(const NormFwdArgs& a, hipStream_t s) {
+  const bool res = a.res != nullptr;
+  const int64_t want = (a.rows + ROW_WAVES - 1) / ROW_WAVES;
+  const int grid = int(want < 4096 ? (want > 0 ? want : 1) : 4096);
+  const DropParams& d = a.drop;
+  with_flags([&](auto RMS, auto RES, auto DROP) {
+    if constexpr (RES || !DROP)
+      with_iters<DTA_NORM_FWD_MAX_COLS>(a.cols, [&](auto I) {
+        norm_fwd_k<I, RMS, RES, DROP><<<grid, 64 * ROW_WAVES, 0, s>>>(
+            a.x, a.res, a.sum_out, a.w, a.b, a.y, a.mean, a.rstd, a.rows,
+            a.cols, a.eps, d.rng, d.site, d.thr16, d.inv_keep);
+      });
+  }, a.rms, res, res && d.thr16 != 0);
 }
-void launch_layernorm_bwd(const bf16_t* dy, const bf16_t* ds,
-                          const bf16_t* x, const bf16_t* w,
-                          const float* mean, const float* rstd, bf16_t* dx,
-                          bf16_t* dres, float* dw, float* db, float* pdw,
-                          float* pdb, int stripes, int64_t rows, int cols,
-                          const unsigned long long* rng,
-                          unsigned long long site, unsigned int thr16,
-                          float ik, hipStream_t s) {
-  if (thr16) {
-    if (ds)
-      dispatch_bwd<false, true, true>(dy, ds, x, w, mean, rstd, dx, dres,
-                                      dw, db, pdw, pdb, stripes, rows,
-                                      cols, rng, site, thr16, ik, s);
-    else
-      dispatch_bwd<false, false, true>(dy, nullptr, x, w, mean, rstd, dx,
-                                       dres, dw, db, pdw, pdb, stripes,
-                                       rows, cols, rng, site, thr16, ik, s);
-  } else if (ds)
-    dispatch_bwd<false, true, false>(dy, ds, x, w, mean, rstd, dx, nullptr,
-                                     dw, db, pdw, pdb, stripes, rows, cols,
-                                     nullptr, 0, 0, 1.f, s);
-  else
-    dispatch_bwd<false, false, false>(dy, nullptr, x, w, mean, rstd, dx,
-                                      nullptr, dw, db, pdw, pdb, stripes,
-                                      rows, cols, nullptr, 0, 0, 1.f, s);
-}
-void launch_rmsnorm_fwd(const bf16_t* x, const bf16_t* res,
-                        bf16_t* sum_out, const bf16_t* w, bf16_t* y,
-                        float* rstd, int64_t rows, int cols, float eps,
-                        const unsigned long long* rng,
-                        unsigned long long site, unsigned int thr16,
-                        float ik, hipStream_t s) {
-  if (res && thr16)
-    dispatch_fwd<true, true, true>(x, res, sum_out, w, nullptr, y, nullptr,
-                                   rstd, rows, cols, eps, rng, site, thr16,
-                                   ik, s);
-  else if (res)
-    dispatch_fwd<true, true, false>(x, res, sum_out, w, nullptr, y,
-                                    nullptr, rstd, rows, cols, eps,
-                                    nullptr, 0, 0, 1.f, s);
-  else
-    dispatch_fwd<true, false, false>(x, nullptr, nullptr, w, nullptr, y,
-                                     nullptr, rstd, rows, cols, eps,
-                                     nullptr, 0, 0, 1.f, s);
-}
-void launch_rmsnorm_bwd(const bf16_t* dy, const bf16_t* ds,
-                        const bf16_t* x, const bf16_t* w,
-                        const float* rstd, bf16_t* dx, bf16_t* dres,
-                        float* dw, float* pdw, int stripes, int64_t rows,
-                        int cols, const unsigned long long* rng,
-                        unsigned long long site, unsigned int thr16,
-                        float ik, hipStream_t s) {
-  if (thr16) {
-    if (ds)
-      dispatch_bwd<true, true, true>(dy, ds, x, w, nullptr, rstd, dx, dres,
-                                     dw, nullptr, pdw, nullptr, stripes,
-                                     rows, cols, rng, site, thr16, ik, s);
-    else
-      dispatch_bwd<true, false, true>(dy, nullptr, x, w, nullptr, rstd, dx,
-                                      dres, dw, nullptr, pdw, nullptr,
-                                      stripes, rows, cols, rng, site,
-                                      thr16, ik, s);
-  } else if (ds)
-    dispatch_bwd<true, true, false>(dy, ds, x, w, nullptr, rstd, dx,
-                                    nullptr, dw, nullptr, pdw, nullptr,
-                                    stripes, rows, cols, nullptr, 0, 0,
-                                    1.f, s);
-  else
-    dispatch_bwd<true, false, false>(dy, nullptr, x, w, nullptr, rstd, dx,
-                                     nullptr, dw, nullptr, pdw, nullptr,
-                                     stripes, rows, cols, nullptr, 0, 0,
-                                     1.f, s);
+
+void launch_norm_bwd(const NormBwdArgs& a, hipStream_t s) {
+  const int grid = dta_norm_bwd_grid(a.rows);
+  const DropParams& d = a.drop;
+  with_flags([&](auto RMS, auto DS, auto DROP, auto FDW) {
+    with_iters<DTA_NORM_BWD_MAX_COLS>(a.cols, [&](auto I) {
+      norm_bwd_dx_k<I, RMS, DS, DROP, FDW><<<grid, 64 * ROW_WAVES, 0, s>>>(
+          a.dy, a.ds, a.x, a.w, a.mean, a.rstd, a.dx, a.dres,
+          FDW ? a.pdw : nullptr, FDW ? a.pdb : nullptr, a.rows, a.cols,
+          d.rng, d.site, d.thr16, d.inv_keep);
+    });
+    if (!FDW) {
+      const ColRedCfg cfg = dta_colred_cfg(a.rows, a.cols);
+      norm_bwd_dwdb_part_k<RMS>
+          <<<dim3(cfg.gx, unsigned(a.stripes)), cfg.threads, 0, s>>>(
+              a.dy, a.x, a.mean, a.rstd, a.pdw, a.pdb, a.rows, a.cols);
+    }
+  }, a.rms, a.ds != nullptr, d.thr16 != 0, dta_norm_fused_dwdb(a.cols));
+  const int g3 = (a.cols / 4 + 255) / 256;
+  // stripe-parallelism scales with the panel height (the fused path
+  // produces up to 4096 panel rows; 32 y-blocks left 128-deep serial
+  // loops on an underfilled chip)
+  const int ry =
+      a.stripes < 32 ? a.stripes : (a.stripes > 1024 ? 256 : 32);
+  dwdb_reduce_k<<<dim3(g3, ry), 256, 0, s>>>(a.pdw, a.pdb, a.dw, a.db,
+                                             a.stripes, a.cols);
 }

@@ -64,7 +64,15 @@ def test_mfma_layout_32x32x16():
 # ---------------------------------------------------------------------------
 # LayerNorm / RMSNorm
 # ---------------------------------------------------------------------------
-@pytest.mark.parametrize("rows,cols", [(128, 768), (64, 64), (33, 4096)])
+# rows=33 is no multiple of the 4 row-waves. cols 8: one active lane; 520: a
+# second iteration with one active lane; 2560 and 3584: 5 and 7 iterations,
+# which the kernels' width table rounds up to 6 and 8.
+_NORM_EDGE = [(33, 8), (33, 520), (33, 2560), (33, 3584)]
+_EMPTY = dict(device=DEV, dtype=torch.bfloat16)
+
+
+@pytest.mark.parametrize("rows,cols", [(128, 768), (64, 64), (33, 4096)]
+                         + _NORM_EDGE)
 def test_layernorm_fwd_bwd(rows, cols):
     m = _ext()
     x = _rand_bf16(rows, cols, seed=1)
@@ -89,7 +97,7 @@ def test_layernorm_fwd_bwd(rows, cols):
                                atol=0.3 * math.sqrt(rows / 128))
 
 
-@pytest.mark.parametrize("rows,cols", [(128, 768), (64, 4096)])
+@pytest.mark.parametrize("rows,cols", [(128, 768), (64, 4096)] + _NORM_EDGE)
 def test_rmsnorm_fwd_bwd(rows, cols):
     m = _ext()
     x = _rand_bf16(rows, cols, seed=1)
@@ -107,6 +115,41 @@ def test_rmsnorm_fwd_bwd(rows, cols):
     dx, dw, _ = m.rmsnorm_bwd(dy, torch.empty(0, device=DEV, dtype=torch.bfloat16), x, w, rstd, _rng(), 0, 0.0)
     torch.testing.assert_close(dx.float(), xr.grad, rtol=5e-2, atol=5e-2)
     torch.testing.assert_close(dw.float(), wr.grad, rtol=5e-2, atol=0.3)
+
+
+@pytest.mark.parametrize("cols", [4104, 8192])
+def test_norm_fwd_wide(cols):
+    """Forward-only widths beyond the backward limit: 9 iterations (rounded
+    up to the 16-iteration kernel) and the full 16."""
+    m = _ext()
+    rows = 33
+    x = _rand_bf16(rows, cols, seed=1)
+    w = _rand_bf16(cols, seed=2, scale=0.5)
+    b = _rand_bf16(cols, seed=3, scale=0.5)
+    xf = x.float()
+    y = m.layernorm_fwd(x, torch.empty(0, **_EMPTY), w, b, 1e-5, _rng(), 0,
+                        0.0)[0]
+    ref = torch.nn.functional.layer_norm(xf, (cols,), w.float(), b.float(),
+                                         1e-5)
+    torch.testing.assert_close(y.float(), ref, rtol=2e-2, atol=2e-2)
+    y = m.rmsnorm_fwd(x, torch.empty(0, **_EMPTY), w, 1e-5, _rng(), 0, 0.0)[0]
+    ref = xf * torch.rsqrt(xf.pow(2).mean(-1, keepdim=True) + 1e-5) * w.float()
+    torch.testing.assert_close(y.float(), ref, rtol=2e-2, atol=2e-2)
+
+
+def test_norm_bwd_rejects_wide_rows():
+    """The backward is instantiated up to 4096 columns; wider rows must
+    raise instead of computing over half the row."""
+    m = _ext()
+    rows, cols = 8, 8192
+    x = _rand_bf16(rows, cols, seed=1)
+    w = _rand_bf16(cols, seed=2)
+    st = torch.ones(rows, device=DEV)
+    e = torch.empty(0, **_EMPTY)
+    with pytest.raises(RuntimeError, match="4096"):
+        m.layernorm_bwd(x, e, x, w, st, st, _rng(), 0, 0.0)
+    with pytest.raises(RuntimeError, match="4096"):
+        m.rmsnorm_bwd(x, e, x, w, st, _rng(), 0, 0.0)
 
 
 # ---------------------------------------------------------------------------
@@ -929,14 +972,15 @@ def test_gpt2_train_dropout_changes_loss_gpu():
     torch.testing.assert_close(e1, e2)    # eval mode: dropout off
 
 
-def test_add_layer_norm_fused_dropout():
+@pytest.mark.parametrize("R,C", [(512, 256), (33, 2560)])
+def test_add_layer_norm_fused_dropout(R, C):
     """Fused residual-branch dropout in add_layer_norm: GPU kernels vs the
     host-gold mask (elementwise chain), fwd and bwd."""
     from distributedtraining_amd import ops
     from distributedtraining_amd.ops import droprng
     droprng.counter(DEV).fill_(31)
     droprng.counter("cpu").fill_(31)
-    R, C, p, site = 512, 256, 0.2, 9
+    p, site = 0.2, 9
     x = _rand_bf16(R, C, seed=50).requires_grad_(True)
     res = _rand_bf16(R, C, seed=51).requires_grad_(True)
     w = _rand_bf16(C, seed=52).requires_grad_(True)
@@ -972,11 +1016,12 @@ def test_add_layer_norm_fused_dropout():
                                rtol=5e-2, atol=0.3)
 
 
-def test_add_rms_norm_fused_dropout():
+@pytest.mark.parametrize("R,C", [(256, 128), (33, 2560)])
+def test_add_rms_norm_fused_dropout(R, C):
     from distributedtraining_amd import ops
     from distributedtraining_amd.ops import droprng
     droprng.counter(DEV).fill_(77)
-    R, C, p, site = 256, 128, 0.3, 4
+    p, site = 0.3, 4
     x = _rand_bf16(R, C, seed=60).requires_grad_(True)
     res = _rand_bf16(R, C, seed=61).requires_grad_(True)
     w = _rand_bf16(C, seed=62).requires_grad_(True)
