@@ -481,8 +481,12 @@ def _dense_last(t: torch.Tensor) -> torch.Tensor:
     return t if t.stride(-1) == 1 else t.contiguous()
 
 
-def _empty_kvlen(t: torch.Tensor) -> torch.Tensor:
-    return torch.empty(0, dtype=torch.int32, device=t.device)
+def _mask_and_counter(kvlen, like: torch.Tensor):
+    """The kvlen tensor the bindings expect (empty = no mask) and the
+    dropout step counter of ``like``'s device."""
+    if kvlen is None:
+        kvlen = torch.empty(0, dtype=torch.int32, device=like.device)
+    return kvlen, droprng.counter(like.device)
 
 
 class _AttnFn(torch.autograd.Function):
@@ -490,8 +494,7 @@ class _AttnFn(torch.autograd.Function):
     def forward(ctx, q, k, v, scale, kvlen, p_drop, site):
         m = require_ext()
         q, k, v = _dense_last(q), _dense_last(k), _dense_last(v)
-        kv = kvlen if kvlen is not None else _empty_kvlen(q)
-        rng = droprng.counter(q.device)
+        kv, rng = _mask_and_counter(kvlen, q)
         o_bshd, lse = m.attn_fwd(q, k, v, scale, kv, rng, site, p_drop)
         ctx.save_for_backward(q, k, v, o_bshd, lse, kv, rng)
         ctx.attn_args = (scale, site, p_drop)
@@ -567,14 +570,18 @@ def causal_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
 # transpose copies anywhere around attention (torch's CatArrayBatchedCopy
 # was 12 launches/step on GPT-2).
 # --------------------------------------------------------------------------
-def _qkv_views(t: torch.Tensor, H: int, Hk: int, D: int):
+def _qkv_views(t: torch.Tensor, H: int, Hk: int, D: int,
+               bshd: bool = False):
+    """q/k/v views of a packed [B,S,(H+2Hk)·D] buffer as [B,heads,S,D], or
+    with ``bshd`` in the memory order [B,S,heads,D]."""
     B, S, Fdim = t.shape
-    sb, ss = S * Fdim, Fdim
-    o0 = t.storage_offset()
-    q = t.as_strided((B, H, S, D), (sb, D, ss, 1), o0)
-    k = t.as_strided((B, Hk, S, D), (sb, D, ss, 1), o0 + H * D)
-    v = t.as_strided((B, Hk, S, D), (sb, D, ss, 1), o0 + (H + Hk) * D)
-    return q, k, v
+
+    def view(heads, off):
+        v = t.as_strided((B, S, heads, D), (S * Fdim, Fdim, D, 1),
+                         t.storage_offset() + off)
+        return v if bshd else v.permute(0, 2, 1, 3)
+
+    return view(H, 0), view(Hk, H * D), view(Hk, (H + Hk) * D)
 
 
 class _QKVAttnFn(torch.autograd.Function):
@@ -584,8 +591,7 @@ class _QKVAttnFn(torch.autograd.Function):
         B, S, Fdim = qkv.shape
         D = Fdim // (H + 2 * Hk)
         q, k, v = _qkv_views(qkv, H, Hk, D)
-        kv = kvlen if kvlen is not None else _empty_kvlen(qkv)
-        rng = droprng.counter(qkv.device)
+        kv, rng = _mask_and_counter(kvlen, qkv)
         o_bshd, lse = m.attn_fwd(q, k, v, scale, kv, rng, site,
                                  p_drop)   # [B,S,H,D] contiguous
         ctx.save_for_backward(qkv, o_bshd, lse, kv, rng)
@@ -603,14 +609,9 @@ class _QKVAttnFn(torch.autograd.Function):
         if do4.stride(3) != 1:
             do4 = do.contiguous().view(B, S, H, D).permute(0, 2, 1, 3)
         dqkv = torch.empty_like(qkv)
-        sb, ss = S * Fdim, Fdim
-        o0 = dqkv.storage_offset()
-        dq_v = dqkv.as_strided((B, S, H, D), (sb, ss, D, 1), o0)
-        dk_v = dqkv.as_strided((B, S, Hk, D), (sb, ss, D, 1), o0 + H * D)
-        dv_v = dqkv.as_strided((B, S, Hk, D), (sb, ss, D, 1),
-                               o0 + (H + Hk) * D)
-        m.attn_bwd_packed(do4, q, k, v, o_bshd, lse, scale, dq_v, dk_v,
-                          dv_v, kv, rng, site, p_drop)
+        m.attn_bwd_packed(do4, q, k, v, o_bshd, lse, scale,
+                          *_qkv_views(dqkv, H, Hk, D, bshd=True),
+                          kv, rng, site, p_drop)
         return dqkv, None, None, None, None, None, None
 
 
@@ -634,11 +635,7 @@ def qkv_attention(qkv: torch.Tensor, n_head: int,
     q = qkv[..., :E].view(B, S, n_head, D).transpose(1, 2)
     k = qkv[..., E:E + kvd].view(B, S, Hk, D).transpose(1, 2)
     v = qkv[..., E + kvd:].view(B, S, Hk, D).transpose(1, 2)
-    if kvlen is None and p_drop <= 0.0:
-        o = F.scaled_dot_product_attention(q, k, v, is_causal=True,
-                                           scale=scale, enable_gqa=True)
-    else:
-        o = _attn_ref(q, k, v, scale, kvlen, p_drop, site)
+    o = causal_attention(q, k, v, scale, kvlen, p_drop, site)
     return o.transpose(1, 2).reshape(B, S, E)
 
 

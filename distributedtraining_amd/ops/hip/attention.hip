@@ -3,20 +3,32 @@
 // the reference's transformers attention (SURVEY.md §2.2 op table; miner
 // seq 64, validator seq 512).
 //
-// Structure (v2):
-//   * one 64-lane wave owns a 16-row Q tile; blocks of 4 independent waves
-//     (no __syncthreads in the loop), grid = (ceil(S/64), B*H).
+// Structure:
+//   * grid = (ceil(S/64), B*H), block = 4 waves = 64 rows of one (b,h):
+//     query rows in fwd/dq, key rows in dkv; each wave owns 16 of them and
+//     keeps their fragments and accumulators in registers.
+//   * The other operand is walked in 32-row tiles that all 256 threads
+//     stage into LDS together, once per iteration, between two
+//     __syncthreads (previous reads done / tile visible):
+//       fwd: K row-major, V transposed
+//       dq:  K row-major + transposed, V row-major
+//       dkv: Q and dO, each row-major + transposed
+//     Row-major panels (pitch D+8) feed A-fragments of the score MFMAs,
+//     transposed [D][LDS_RP] panels feed B-fragments of the accumulating
+//     MFMAs as single 16 B LDS reads.
+//   * Barrier-uniform loops: the trip count depends on blockIdx only, and
+//     a wave with nothing to do in an iteration `continue`s AFTER the
+//     second barrier. Nothing returns or breaks before a __syncthreads.
 //   * STRIDE-AWARE addressing: q/k/v/o are consumed as [B,H,S,D] *views*
 //     of the projection output [B,S,H*D] (and dq/dk/dv written the same
 //     way) so the model layer does zero transpose/contiguous copies.
 //   * GQA native: kv head = h / group; no repeat_interleave materialization.
-//   * row fragments stream from global (K/V fit in L2 at these seq
-//     lengths); k-major B-fragments are NOT gathered from global (8 scalar
-//     2B loads each, ~32x line waste) — row frags are scatter-stored
-//     transposed into wave-private LDS and re-read as 16B vectors.
 //   * swapped QK^T: mfma(A=K_tile, B=Q^T) puts a query's scores in lanes
 //     sharing (lane&15) so the softmax row-reduce is two shfl_xor ops;
 //     exp via the single-instruction exp2 path.
+//   * One copy each of the mask rule (attn_visible), the dropout draw of a
+//     32-key tile (attn_drop_hashes/attn_drop_apply) and the accumulator
+//     walk (for_acc_rows); the host gold mirrors them in ops/droprng.py.
 //
 // Fragment maps (verified on-device by mfma_selftest, tests/test_ops_gpu.py):
 //   mfma_f32_16x16x32_bf16: A[i][k]: i=lane&15, k=8*(lane>>4)+j (j=0..7)
@@ -25,84 +37,117 @@
 #include "dta_common.h"
 #include "dta_kernels.h"
 
+#include <type_traits>
+
 namespace {
 
-DEV f32x4 mfma_bf16(bf16x8 a, bf16x8 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
+// ---- per-block context ------------------------------------------------------
+// What the three training kernels derive the same way from the geometry and
+// the block/thread ids. Which 64-row tile the block owns is the kernel's.
+struct AttnCtx {
+  int tid, lane, wid, g;            // g = lane >> 4: MFMA lane group
+  int b, h, hk;
+  int64_t bhid;                     // b * H + h: row of lse/delta, RNG head
+  const ushort *q, *k, *v, *dout;   // (b, h | hk) base pointers
+  float sc2;                        // scale folded into the exp2 argument
+  int kvl;                          // keys >= kvl are padding (block-uniform)
+  uint32_t thr;                     // dropout threshold, 0 = off
+  uint64_t drop_s2;                 // per-head dropout seed
+};
+
+// dout may be null (forward); its strides are then 0.
+DEV AttnCtx attn_ctx(const AttnGeom& geo, const ushort* q, const ushort* k,
+                     const ushort* v, const ushort* dout) {
+  AttnCtx c;
+  c.tid = threadIdx.x;
+  c.lane = c.tid & 63;
+  c.wid = c.tid >> 6;
+  c.g = c.lane >> 4;
+  c.bhid = blockIdx.y;
+  c.b = int(c.bhid) / geo.H;
+  c.h = int(c.bhid) % geo.H;
+  c.hk = c.h / geo.grp;
+  c.q = q + c.b * geo.q.batch + c.h * geo.q.head;
+  c.k = k + c.b * geo.k.batch + c.hk * geo.k.head;
+  c.v = v + c.b * geo.v.batch + c.hk * geo.v.head;
+  c.dout = dout + c.b * geo.dout.batch + c.h * geo.dout.head;
+  c.sc2 = geo.scale * LOG2E;
+  c.kvl = geo.kvlen ? min(geo.seq, geo.kvlen[c.b]) : geo.seq;
+  c.thr = geo.drop.thr16;
+  c.drop_s2 = 0;
+  if (c.thr)
+    c.drop_s2 = rng_head_seed(rng_site_seed(geo.drop.rng, geo.drop.site),
+                              uint64_t(c.bhid));
+  return c;
 }
+
+// key k is visible to query q: causal, and not padding of this batch row
+DEV bool attn_visible(int q, int k, int kvl) { return k <= q && k < kvl; }
+
+// Rows past seq are loaded from the last row instead: garbage, but in
+// bounds, and safe everywhere because the matching score/probability lanes
+// are masked to 0.
+DEV int clamp_row(int row, int seq) { return row < seq ? row : seq - 1; }
+
+// ---- dropout of a 32-key score tile (fwd, dq) -------------------------------
+// A lane holds keys kv0 + 4g + r and kv0 + 16 + 4g + r (r = 0..3) of query
+// qrow: one hash covers the 4 consecutive keys of each half (k & 3 == r).
+struct DropHashes { uint64_t h0, h1; };
+DEV DropHashes attn_drop_hashes(const AttnCtx& c, int qrow, int kv0) {
+  const uint64_t hq = rng_attn_row(c.drop_s2, uint32_t(qrow));
+  return {rng_attn_row_hash(hq, uint32_t((kv0 + 4 * c.g) >> 2)),
+          rng_attn_row_hash(hq, uint32_t((kv0 + 16 + 4 * c.g) >> 2))};
+}
+// keep-or-zero of the element in hash slot r (k & 3), unbiased rescale
+DEV float attn_drop_keep(float x, uint64_t h, int r, const DropParams& d) {
+  return rng_keep(h, r, d.thr16) ? x * d.inv_keep : 0.f;
+}
+
+// ---- fragments and LDS tile staging ----------------------------------------
+// B-fragments (k-major columns) gathered straight from global memory cost 8
+// scalar 2 B loads each, every one touching its own 64 B line (~32x wasted
+// HBM traffic — measured 204 us on the dkv kernel), and loading tiles per
+// wave re-read ~590 MB/step from L2/HBM at the flagship shape. So the 4
+// waves stage each 32-row tile once, cooperatively.
+constexpr int LDS_RP = 40;  // 32 rows + 8 pad (multiple of 8: aligned reads)
+// Row-major pitch: D+8 (2-way max bank conflict on 16-row A reads).
+template <int DTILES> constexpr int LDS_RM_PITCH = 16 * DTILES + 8;
+template <int DTILES> constexpr int LDS_RM_SIZE = 32 * LDS_RM_PITCH<DTILES>;
+template <int DTILES> constexpr int LDS_T_SIZE = 16 * DTILES * LDS_RP;
 
 DEV bf16x8 load_frag_row(const ushort* base, int64_t row_stride, int row,
                          int col0) {
-  const s16x8 v =
-      *reinterpret_cast<const s16x8*>(base + int64_t(row) * row_stride + col0);
-  union { s16x8 s; bf16x8 b; } u;
-  u.s = v;
-  return u.b;
+  return as_bf16x8(*reinterpret_cast<const s16x8*>(
+      base + int64_t(row) * row_stride + col0));
 }
-
-// ---- LDS tile staging ------------------------------------------------------
-// B-fragments (k-major columns) gathered straight from global memory cost 8
-// scalar 2 B loads each, every one touching its own 64 B line (~32x wasted
-// HBM traffic — measured 204 us on the dkv kernel). Tiles are staged
-// block-cooperatively (the 4 waves share one (b,h)'s K/V or Q/dO) as
-// row-major panels for A-fragments and transposed [cols][LDS_RP] panels
-// for B-fragments (single 16 B LDS reads). Rows beyond seq hold clamped
-// garbage — safe everywhere because the matching score/probability lanes
-// are already masked to 0 upstream.
-constexpr int LDS_RP = 40;  // 32 rows + 8 pad (multiple of 8: aligned reads)
-
 DEV bf16x8 load_frag_col_lds(const ushort* lds_t, int row0, int col) {
-  const s16x8 v =
-      *reinterpret_cast<const s16x8*>(lds_t + col * LDS_RP + row0);
-  union { s16x8 s; bf16x8 b; } u;
-  u.s = v;
-  return u.b;
+  return as_bf16x8(
+      *reinterpret_cast<const s16x8*>(lds_t + col * LDS_RP + row0));
 }
-
-// ---- block-cooperative tile staging ---------------------------------------
-// The 4 waves of a block share one (b,h)'s K/V (fwd, dq) or Q/dO (dkv)
-// tiles; loading them per wave re-read ~590 MB/step from L2/HBM at the
-// flagship shape. All 256 threads cooperatively stage the 32-row tile
-// once per iteration (row-major for A-fragments, transposed for
-// B-fragments); rows past seq are clamped (masked upstream).
-// Row-major pitch: D+8 (2-way max bank conflict on 16-row A reads).
-template <int DTILES>
-DEV void stage_tile_rm(ushort* lds_rm, const ushort* src, int64_t rstride,
-                       int row0, int seq, int tid) {
-  constexpr int CPR = 2 * DTILES;       // 16B chunks per row (D/8)
-  constexpr int RP = 16 * DTILES + 8;
-  for (int i = tid; i < 32 * CPR; i += 256) {
-    const int r = i / CPR, c8 = (i % CPR) * 8;
-    const int rr = row0 + r;
-    const s16x8 v = *reinterpret_cast<const s16x8*>(
-        src + int64_t(rr < seq ? rr : seq - 1) * rstride + c8);
-    *reinterpret_cast<s16x8*>(lds_rm + r * RP + c8) = v;
-  }
-}
-
-template <int DTILES>
-DEV void stage_tile_T2(ushort* lds_t, const ushort* src, int64_t rstride,
-                       int row0, int seq, int tid) {
-  constexpr int CPR = 2 * DTILES;
-  for (int i = tid; i < 32 * CPR; i += 256) {
-    const int r = i / CPR, c8 = (i % CPR) * 8;
-    const int rr = row0 + r;
-    const s16x8 v = *reinterpret_cast<const s16x8*>(
-        src + int64_t(rr < seq ? rr : seq - 1) * rstride + c8);
-#pragma unroll
-    for (int j = 0; j < 8; ++j)
-      lds_t[(c8 + j) * LDS_RP + r] = ushort(v[j]);
-  }
-}
-
 template <int DTILES>
 DEV bf16x8 load_frag_rm(const ushort* lds_rm, int row_rel, int c0) {
-  constexpr int RP = 16 * DTILES + 8;
-  const s16x8 v =
-      *reinterpret_cast<const s16x8*>(lds_rm + row_rel * RP + c0);
-  union { s16x8 s; bf16x8 b; } u;
-  u.s = v;
-  return u.b;
+  return as_bf16x8(*reinterpret_cast<const s16x8*>(
+      lds_rm + row_rel * LDS_RM_PITCH<DTILES> + c0));
+}
+
+// Stage rows row0..row0+31 of a [seq, D] operand into LDS, row-major or
+// TRANSPOSEd, one clamped 16 B global load per chunk.
+template <int DTILES, bool TRANSPOSE>
+DEV void stage_tile(ushort* lds, const ushort* src, int64_t rstride,
+                    int row0, int seq, int tid) {
+  constexpr int CPR = 2 * DTILES;       // 16B chunks per row (D/8)
+  for (int i = tid; i < 32 * CPR; i += 256) {
+    const int r = i / CPR, c8 = (i % CPR) * 8;
+    const s16x8 v = *reinterpret_cast<const s16x8*>(
+        src + int64_t(clamp_row(row0 + r, seq)) * rstride + c8);
+    if constexpr (TRANSPOSE) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j)
+        lds[(c8 + j) * LDS_RP + r] = ushort(v[j]);
+    } else {
+      *reinterpret_cast<s16x8*>(lds + r * LDS_RM_PITCH<DTILES> + c8) = v;
+    }
+  }
 }
 
 DEV bf16x8 pack_bf16x8(const float* f) {
@@ -133,66 +178,70 @@ DEV bf16x8 scores_to_afrag(const f32x4& p0, const f32x4& p1, int lane) {
   return pack_bf16x8(pa);
 }
 
+// ---- accumulator epilogue ---------------------------------------------------
+// Walk a wave's [16, D] accumulator in C layout: f(t, r, row, col) for
+// every element whose row (row0 + 4g + r) is below seq.
+template <int DTILES, class F>
+DEV void for_acc_rows(int row0, int seq, int lane, F f) {
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int row = row0 + 4 * (lane >> 4) + r;
+    if (row >= seq) continue;
+#pragma unroll
+    for (int t = 0; t < DTILES; ++t) f(t, r, row, 16 * t + (lane & 15));
+  }
+}
+// dst[row, col] = bf16(acc * fac[r]) for o and dq; dst is their (b, h) base
+template <int DTILES>
+DEV void store_acc_tile(ushort* dst, int64_t rstride, int row0, int seq,
+                        int lane, const f32x4* acc, f32x4 fac) {
+  for_acc_rows<DTILES>(row0, seq, lane, [&](int t, int r, int row, int col) {
+    dst[int64_t(row) * rstride + col] = f2bf(acc[t][r] * fac[r]);
+  });
+}
+
 // ---------------- forward ----------------
-// Block = 4 waves = 64 q rows of one (b,h); K/V tiles staged ONCE per
-// block per 32-key iteration (cooperative, barrier-synchronized — every
-// thread reaches both __syncthreads regardless of seq masking).
+// K (row-major) and V (transposed) tiles are staged once per block per
+// 32-key iteration.
 template <int DTILES>  // D = 16*DTILES
 __global__ void attn_fwd_k(const ushort* __restrict__ q,
                            const ushort* __restrict__ k,
                            const ushort* __restrict__ v,
                            ushort* __restrict__ o, float* __restrict__ lse,
                            AttnGeom geo) {
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wid = tid >> 6;
-  const int64_t bhid = blockIdx.y;
-  const int b = int(bhid) / geo.H, h = int(bhid) % geo.H;
-  const int hk = h / geo.grp;
-  const int seq = geo.seq;
-  const int q0 = blockIdx.x * 64 + wid * 16;
+  const AttnCtx c = attn_ctx(geo, q, k, v, nullptr);
+  const int lane = c.lane, g = c.g, seq = geo.seq, kvl = c.kvl;
+  const int q0 = blockIdx.x * 64 + c.wid * 16;
   const bool live = q0 < seq;
-  const ushort* qp = q + b * geo.qb + h * geo.qh;
-  const ushort* kp = k + b * geo.kb + hk * geo.kh;
-  const ushort* vp = v + b * geo.vb + hk * geo.vh;
-  const float sc2 = geo.scale * LOG2E;  // fold scale into the exp2 argument
-  // padded batches: keys >= kvl are masked for every query (block-uniform)
-  const int kvl = geo.kvlen ? min(seq, geo.kvlen[b]) : seq;
-  const uint32_t thr = geo.drop.thr16;
-  uint64_t drop_s2 = 0;
-  if (thr)
-    drop_s2 = rng_head_seed(rng_site_seed(geo.drop.rng, geo.drop.site),
-                            uint64_t(bhid));
+  const int qrow = q0 + (lane & 15);
 
   bf16x8 qb_[DTILES / 2];
-  const int qrow = q0 + (lane & 15);
-  const int qr_ld = qrow < seq ? qrow : seq - 1;
 #pragma unroll
   for (int sl = 0; sl < DTILES / 2; ++sl)
-    qb_[sl] = load_frag_row(qp, geo.qs, qr_ld, 32 * sl + 8 * (lane >> 4));
+    qb_[sl] = load_frag_row(c.q, geo.q.seq, clamp_row(qrow, seq),
+                            32 * sl + 8 * g);
 
   f32x4 acc[DTILES];
 #pragma unroll
   for (int t = 0; t < DTILES; ++t) acc[t] = f32x4{0, 0, 0, 0};
   float m_run = -INFINITY, l_run = 0.f;  // in exp2 units
 
-  __shared__ ushort k_rm[32 * (16 * DTILES + 8)];
-  __shared__ ushort v_t[16 * DTILES * LDS_RP];
-  const int g = lane >> 4;
+  __shared__ ushort k_rm[LDS_RM_SIZE<DTILES>];
+  __shared__ ushort v_t[LDS_T_SIZE<DTILES>];
   // loop + mask bounds honor the pad length (kvl == seq when unmasked)
   const int blk_kv_end =
       min(min(seq, int(blockIdx.x) * 64 + 64), (kvl + 31) & ~31);  // uniform
   const int my_kv_end = live ? min(seq, q0 + 16) : 0;
   for (int kv0 = 0; kv0 < blk_kv_end; kv0 += 32) {
     __syncthreads();   // previous iteration's LDS reads complete
-    stage_tile_rm<DTILES>(k_rm, kp, geo.ks, kv0, seq, tid);
-    stage_tile_T2<DTILES>(v_t, vp, geo.vs, kv0, seq, tid);
+    stage_tile<DTILES, false>(k_rm, c.k, geo.k.seq, kv0, seq, c.tid);
+    stage_tile<DTILES, true>(v_t, c.v, geo.v.seq, kv0, seq, c.tid);
     __syncthreads();
     if (kv0 >= my_kv_end) continue;   // after barriers: uniform safety
     f32x4 p0 = {0, 0, 0, 0}, p1 = {0, 0, 0, 0};
 #pragma unroll
     for (int sl = 0; sl < DTILES / 2; ++sl) {
-      const int c0 = 32 * sl + 8 * (lane >> 4);
+      const int c0 = 32 * sl + 8 * g;
       bf16x8 ka = load_frag_rm<DTILES>(k_rm, lane & 15, c0);
       p0 = mfma_bf16(ka, qb_[sl], p0);
       bf16x8 kb2 = load_frag_rm<DTILES>(k_rm, 16 + (lane & 15), c0);
@@ -202,8 +251,8 @@ __global__ void attn_fwd_k(const ushort* __restrict__ q,
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int k0a = kv0 + 4 * g + r, k1a = k0a + 16;
-      p0[r] = (k0a <= qrow && k0a < kvl) ? p0[r] * sc2 : -INFINITY;
-      p1[r] = (k1a <= qrow && k1a < kvl) ? p1[r] * sc2 : -INFINITY;
+      p0[r] = attn_visible(qrow, k0a, kvl) ? p0[r] * c.sc2 : -INFINITY;
+      p1[r] = attn_visible(qrow, k1a, kvl) ? p1[r] * c.sc2 : -INFINITY;
       mx = fmaxf(mx, fmaxf(p0[r], p1[r]));
     }
     mx = fmaxf(mx, __shfl_xor(mx, 16));
@@ -223,19 +272,14 @@ __global__ void attn_fwd_k(const ushort* __restrict__ q,
     l_run = l_run * alpha + psum;
     m_run = m_new;
 
-    if (thr) {
+    if (c.thr) {
       // dropout on the PV accumulation only: l keeps the undropped sum,
-      // so O = dropout(P) V with P the true softmax. One hash covers the
-      // 4 consecutive keys this lane holds per half (k & 3 == r).
-      const uint64_t hq = rng_attn_row(drop_s2, uint32_t(qrow));
-      const uint64_t h0 =
-          rng_attn_row_hash(hq, uint32_t((kv0 + 4 * g) >> 2));
-      const uint64_t h1 =
-          rng_attn_row_hash(hq, uint32_t((kv0 + 16 + 4 * g) >> 2));
+      // so O = dropout(P) V with P the true softmax
+      const DropHashes dh = attn_drop_hashes(c, qrow, kv0);
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        p0[r] = rng_keep(h0, r, thr) ? p0[r] * geo.drop.inv_keep : 0.f;
-        p1[r] = rng_keep(h1, r, thr) ? p1[r] * geo.drop.inv_keep : 0.f;
+        p0[r] = attn_drop_keep(p0[r], dh.h0, r, geo.drop);
+        p1[r] = attn_drop_keep(p1[r], dh.h1, r, geo.drop);
       }
     }
     bf16x8 pa = scores_to_afrag(p0, p1, lane);
@@ -254,28 +298,20 @@ __global__ void attn_fwd_k(const ushort* __restrict__ q,
   if (!live) return;
   // epilogue: O /= l; lse stored in NATURAL-log units = (m + log2 l)*ln2
   if (lane < 16 && qrow < seq)
-    lse[bhid * seq + qrow] = (m_run + __builtin_log2f(l_run)) * LN2;
-  float inv[4];
+    lse[c.bhid * seq + qrow] = (m_run + __builtin_log2f(l_run)) * LN2;
+  f32x4 inv;
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     float lr = __shfl(l_run, 4 * g + r);
     inv[r] = lr > 0.f ? 1.0f / lr : 0.f;
   }
-  ushort* op = o + b * geo.ob + h * geo.oh;
-#pragma unroll
-  for (int t = 0; t < DTILES; ++t)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int orow = q0 + 4 * g + r;
-      if (orow < seq)
-        op[int64_t(orow) * geo.os_ + 16 * t + (lane & 15)] =
-            f2bf(acc[t][r] * inv[r]);
-    }
+  store_acc_tile<DTILES>(o + c.b * geo.o.batch + c.h * geo.o.head, geo.o.seq,
+                         q0, seq, lane, acc, inv);
 }
 
 // ---------------- backward dQ ----------------
-// Same cooperative structure as forward: K (row-major + transposed) and V
-// (row-major) staged once per block per 32-key iteration.
+// K (row-major + transposed) and V (row-major) staged once per block per
+// 32-key iteration.
 // Also COMPUTES delta[q] = rowsum(dO[q]*O[q]) from its own rows (it loads
 // dO anyway; O rows are one extra coalesced read) and publishes it for the
 // dkv kernel — the standalone delta kernel is gone.
@@ -285,41 +321,25 @@ __global__ void attn_bwd_dq_k(const ushort* __restrict__ dout,
                               const ushort* __restrict__ k,
                               const ushort* __restrict__ v,
                               const ushort* __restrict__ o,
-                              int64_t ob2, int64_t oh2, int64_t os2,
                               const float* __restrict__ lse,
                               float* __restrict__ delta,
                               ushort* __restrict__ dq, AttnGeom geo) {
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wid = tid >> 6;
-  const int64_t bhid = blockIdx.y;
-  const int b = int(bhid) / geo.H, h = int(bhid) % geo.H;
-  const int hk = h / geo.grp;
-  const int seq = geo.seq;
-  const int q0 = blockIdx.x * 64 + wid * 16;
+  const AttnCtx c = attn_ctx(geo, q, k, v, dout);
+  const int lane = c.lane, g = c.g, seq = geo.seq, kvl = c.kvl;
+  const int q0 = blockIdx.x * 64 + c.wid * 16;
   const bool live = q0 < seq;
-  const ushort* qp = q + b * geo.qb + h * geo.qh;
-  const ushort* kp = k + b * geo.kb + hk * geo.kh;
-  const ushort* vp = v + b * geo.vb + hk * geo.vh;
-  const ushort* dop = dout + b * geo.db_ + h * geo.dh;
-  const ushort* op2 = o + b * ob2 + h * oh2;
-  const int kvl = geo.kvlen ? min(seq, geo.kvlen[b]) : seq;
-  const uint32_t thr = geo.drop.thr16;
-  uint64_t drop_s2 = 0;
-  if (thr)
-    drop_s2 = rng_head_seed(rng_site_seed(geo.drop.rng, geo.drop.site),
-                            uint64_t(bhid));
-
   const int qrow = q0 + (lane & 15);
-  const int qr_ld = qrow < seq ? qrow : seq - 1;
+  const int qr_ld = clamp_row(qrow, seq);
+  const ushort* op = o + c.b * geo.o.batch + c.h * geo.o.head;
+
   bf16x8 qb_[DTILES / 2], dob[DTILES / 2];
   float dpart = 0.f;
 #pragma unroll
   for (int sl = 0; sl < DTILES / 2; ++sl) {
-    const int c0 = 32 * sl + 8 * (lane >> 4);
-    qb_[sl] = load_frag_row(qp, geo.qs, qr_ld, c0);
-    dob[sl] = load_frag_row(dop, geo.ds, qr_ld, c0);
-    bf16x8 orow = load_frag_row(op2, os2, qr_ld, c0);
+    const int c0 = 32 * sl + 8 * g;
+    qb_[sl] = load_frag_row(c.q, geo.q.seq, qr_ld, c0);
+    dob[sl] = load_frag_row(c.dout, geo.dout.seq, qr_ld, c0);
+    bf16x8 orow = load_frag_row(op, geo.o.seq, qr_ld, c0);
 #pragma unroll
     for (int j = 0; j < 8; ++j)
       dpart = fmaf(float(dob[sl][j]), float(orow[j]), dpart);
@@ -329,33 +349,31 @@ __global__ void attn_bwd_dq_k(const ushort* __restrict__ dout,
   dpart += __shfl_xor(dpart, 16);
   dpart += __shfl_xor(dpart, 32);
   const float dlt_q = dpart;
-  if (lane < 16 && qrow < seq) delta[bhid * seq + qrow] = dlt_q;
-  const float lse_q = lse[bhid * seq + qr_ld] * LOG2E;  // exp2 units
-  const float sc2 = geo.scale * LOG2E;
+  if (lane < 16 && qrow < seq) delta[c.bhid * seq + qrow] = dlt_q;
+  const float lse_q = lse[c.bhid * seq + qr_ld] * LOG2E;  // exp2 units
 
   f32x4 acc[DTILES];
 #pragma unroll
   for (int t = 0; t < DTILES; ++t) acc[t] = f32x4{0, 0, 0, 0};
 
-  __shared__ ushort k_rm[32 * (16 * DTILES + 8)];
-  __shared__ ushort v_rm[32 * (16 * DTILES + 8)];
-  __shared__ ushort k_t[16 * DTILES * LDS_RP];
-  const int g = lane >> 4;
+  __shared__ ushort k_rm[LDS_RM_SIZE<DTILES>];
+  __shared__ ushort v_rm[LDS_RM_SIZE<DTILES>];
+  __shared__ ushort k_t[LDS_T_SIZE<DTILES>];
   const int blk_kv_end =
       min(min(seq, int(blockIdx.x) * 64 + 64), (kvl + 31) & ~31);  // uniform
   const int my_kv_end = live ? min(seq, q0 + 16) : 0;
   for (int kv0 = 0; kv0 < blk_kv_end; kv0 += 32) {
     __syncthreads();
-    stage_tile_rm<DTILES>(k_rm, kp, geo.ks, kv0, seq, tid);
-    stage_tile_rm<DTILES>(v_rm, vp, geo.vs, kv0, seq, tid);
-    stage_tile_T2<DTILES>(k_t, kp, geo.ks, kv0, seq, tid);
+    stage_tile<DTILES, false>(k_rm, c.k, geo.k.seq, kv0, seq, c.tid);
+    stage_tile<DTILES, false>(v_rm, c.v, geo.v.seq, kv0, seq, c.tid);
+    stage_tile<DTILES, true>(k_t, c.k, geo.k.seq, kv0, seq, c.tid);
     __syncthreads();
     if (kv0 >= my_kv_end) continue;
     f32x4 s0 = {0, 0, 0, 0}, s1 = {0, 0, 0, 0};
     f32x4 dp0 = {0, 0, 0, 0}, dp1 = {0, 0, 0, 0};
 #pragma unroll
     for (int sl = 0; sl < DTILES / 2; ++sl) {
-      const int c0 = 32 * sl + 8 * (lane >> 4);
+      const int c0 = 32 * sl + 8 * g;
       bf16x8 ka = load_frag_rm<DTILES>(k_rm, lane & 15, c0);
       bf16x8 kb2 = load_frag_rm<DTILES>(k_rm, 16 + (lane & 15), c0);
       bf16x8 va = load_frag_rm<DTILES>(v_rm, lane & 15, c0);
@@ -365,28 +383,25 @@ __global__ void attn_bwd_dq_k(const ushort* __restrict__ dout,
       dp0 = mfma_bf16(va, dob[sl], dp0);
       dp1 = mfma_bf16(vb2, dob[sl], dp1);
     }
-    uint64_t h0 = 0, h1 = 0;
-    if (thr) {
-      const uint64_t hq = rng_attn_row(drop_s2, uint32_t(qrow));
-      h0 = rng_attn_row_hash(hq, uint32_t((kv0 + 4 * g) >> 2));
-      h1 = rng_attn_row_hash(hq, uint32_t((kv0 + 16 + 4 * g) >> 2));
+    // dS = P ⊙ (M/(1-p) ⊙ (dO Vᵀ) − delta): the dropout mask gates the
+    // dO·V term only; delta = rowsum(dO ⊙ O) already absorbs the mask
+    if (c.thr) {
+      const DropHashes dh = attn_drop_hashes(c, qrow, kv0);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        dp0[r] = attn_drop_keep(dp0[r], dh.h0, r, geo.drop);
+        dp1[r] = attn_drop_keep(dp1[r], dh.h1, r, geo.drop);
+      }
     }
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int k0a = kv0 + 4 * g + r, k1a = k0a + 16;
-      const bool v0 = (k0a <= qrow && k0a < kvl);
-      const bool v1 = (k1a <= qrow && k1a < kvl);
-      const float P0 = v0 ? __builtin_exp2f(s0[r] * sc2 - lse_q) : 0.f;
-      const float P1 = v1 ? __builtin_exp2f(s1[r] * sc2 - lse_q) : 0.f;
-      // dS = P ⊙ (M/(1-p) ⊙ (dO Vᵀ) − delta): the dropout mask gates the
-      // dO·V term only; delta = rowsum(dO ⊙ O) already absorbs the mask
-      float g0 = dp0[r], g1 = dp1[r];
-      if (thr) {
-        g0 = rng_keep(h0, r, thr) ? g0 * geo.drop.inv_keep : 0.f;
-        g1 = rng_keep(h1, r, thr) ? g1 * geo.drop.inv_keep : 0.f;
-      }
-      s0[r] = P0 * (g0 - dlt_q);
-      s1[r] = P1 * (g1 - dlt_q);
+      const float P0 = attn_visible(qrow, k0a, kvl)
+                           ? __builtin_exp2f(s0[r] * c.sc2 - lse_q) : 0.f;
+      const float P1 = attn_visible(qrow, k1a, kvl)
+                           ? __builtin_exp2f(s1[r] * c.sc2 - lse_q) : 0.f;
+      s0[r] = P0 * (dp0[r] - dlt_q);
+      s1[r] = P1 * (dp1[r] - dlt_q);
     }
     bf16x8 dsa = scores_to_afrag(s0, s1, lane);
 #pragma unroll
@@ -396,26 +411,18 @@ __global__ void attn_bwd_dq_k(const ushort* __restrict__ dout,
     }
   }
   if (!live) return;
-  ushort* dqp = dq + b * geo.ob + h * geo.oh;  // dq uses o-geometry strides
-#pragma unroll
-  for (int t = 0; t < DTILES; ++t)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int orow = q0 + 4 * g + r;
-      if (orow < seq)
-        dqp[int64_t(orow) * geo.os_ + 16 * t + (lane & 15)] =
-            f2bf(acc[t][r] * geo.scale);
-    }
+  store_acc_tile<DTILES>(dq + c.b * geo.dq.batch + c.h * geo.dq.head,
+                         geo.dq.seq, q0, seq, lane, acc,
+                         f32x4{geo.scale, geo.scale, geo.scale, geo.scale});
 }
 
 // ---------------- backward dK/dV ----------------
-// Block = 4 waves = 64 KV rows of one (b,h); Q/dO tiles staged once per
-// block per 32-query iteration (row-major for the score mfmas, transposed
-// for the accumulation B-fragments). With GQA (grp>1) each kv head is
-// walked once per ATTACHED q head (blockIdx.y covers B*H) and results are
-// accumulated with fp32 atomics into dk/dv. Early waves see a few
-// below-diagonal query tiles (probabilities masked to 0) — the price of a
-// uniform, barrier-safe loop.
+// Q/dO tiles staged once per block per 32-query iteration (row-major for
+// the score mfmas, transposed for the accumulation B-fragments). With GQA
+// (grp>1) each kv head is walked once per ATTACHED q head (blockIdx.y
+// covers B*H) and results are accumulated with fp32 atomics into dk/dv.
+// Early waves see a few below-diagonal query tiles (probabilities masked
+// to 0) — the price of a uniform, barrier-safe loop.
 template <int DTILES, bool ATOMIC>
 __global__ void attn_bwd_dkv_k(const ushort* __restrict__ dout,
                                const ushort* __restrict__ q,
@@ -427,34 +434,19 @@ __global__ void attn_bwd_dkv_k(const ushort* __restrict__ dout,
                                float* __restrict__ dv32,
                                ushort* __restrict__ dk,
                                ushort* __restrict__ dv, AttnGeom geo) {
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wid = tid >> 6;
-  const int64_t bhid = blockIdx.y;
-  const int b = int(bhid) / geo.H, h = int(bhid) % geo.H;
-  const int hk = h / geo.grp;
-  const int seq = geo.seq;
-  const int kv0 = blockIdx.x * 64 + wid * 16;
+  const AttnCtx c = attn_ctx(geo, q, k, v, dout);
+  const int lane = c.lane, g = c.g, seq = geo.seq, kvl = c.kvl;
+  const int kv0 = blockIdx.x * 64 + c.wid * 16;
   const bool live = kv0 < seq;
-  const ushort* qp = q + b * geo.qb + h * geo.qh;
-  const ushort* kp = k + b * geo.kb + hk * geo.kh;
-  const ushort* vp = v + b * geo.vb + hk * geo.vh;
-  const ushort* dop = dout + b * geo.db_ + h * geo.dh;
-  const float sc2 = geo.scale * LOG2E;
-  const int kvl = geo.kvlen ? min(seq, geo.kvlen[b]) : seq;
-  const uint32_t thr = geo.drop.thr16;
-  uint64_t drop_s2 = 0;
-  if (thr)
-    drop_s2 = rng_head_seed(rng_site_seed(geo.drop.rng, geo.drop.site),
-                            uint64_t(bhid));
-
   const int krow = kv0 + (lane & 15);
-  const int kr_ld = krow < seq ? krow : seq - 1;
+
   bf16x8 kb_[DTILES / 2], vbf[DTILES / 2];
 #pragma unroll
   for (int sl = 0; sl < DTILES / 2; ++sl) {
-    kb_[sl] = load_frag_row(kp, geo.ks, kr_ld, 32 * sl + 8 * (lane >> 4));
-    vbf[sl] = load_frag_row(vp, geo.vs, kr_ld, 32 * sl + 8 * (lane >> 4));
+    kb_[sl] = load_frag_row(c.k, geo.k.seq, clamp_row(krow, seq),
+                            32 * sl + 8 * g);
+    vbf[sl] = load_frag_row(c.v, geo.v.seq, clamp_row(krow, seq),
+                            32 * sl + 8 * g);
   }
 
   f32x4 acck[DTILES], accv[DTILES];
@@ -464,29 +456,27 @@ __global__ void attn_bwd_dkv_k(const ushort* __restrict__ dout,
     accv[t] = f32x4{0, 0, 0, 0};
   }
 
-  __shared__ ushort q_rm[32 * (16 * DTILES + 8)];
-  __shared__ ushort d_rm[32 * (16 * DTILES + 8)];
-  __shared__ ushort q_t[16 * DTILES * LDS_RP];
-  __shared__ ushort d_t[16 * DTILES * LDS_RP];
-  const int g = lane >> 4;
+  __shared__ ushort q_rm[LDS_RM_SIZE<DTILES>];
+  __shared__ ushort d_rm[LDS_RM_SIZE<DTILES>];
+  __shared__ ushort q_t[LDS_T_SIZE<DTILES>];
+  __shared__ ushort d_t[LDS_T_SIZE<DTILES>];
   // a block whose 64 key rows are all padding has zero dk/dv: skip the
   // whole walk (uniform) and fall through to the zero-initialized stores
   const int q_start =
       (int(blockIdx.x) * 64 >= kvl) ? seq : int(blockIdx.x) * 64;
-  const bool kv_ok = krow < kvl;
   for (int q0 = q_start; q0 < seq; q0 += 32) {
     __syncthreads();
-    stage_tile_rm<DTILES>(q_rm, qp, geo.qs, q0, seq, tid);
-    stage_tile_rm<DTILES>(d_rm, dop, geo.ds, q0, seq, tid);
-    stage_tile_T2<DTILES>(q_t, qp, geo.qs, q0, seq, tid);
-    stage_tile_T2<DTILES>(d_t, dop, geo.ds, q0, seq, tid);
+    stage_tile<DTILES, false>(q_rm, c.q, geo.q.seq, q0, seq, c.tid);
+    stage_tile<DTILES, false>(d_rm, c.dout, geo.dout.seq, q0, seq, c.tid);
+    stage_tile<DTILES, true>(q_t, c.q, geo.q.seq, q0, seq, c.tid);
+    stage_tile<DTILES, true>(d_t, c.dout, geo.dout.seq, q0, seq, c.tid);
     __syncthreads();
     if (!live || q0 + 31 < kv0) continue;   // fully below the diagonal
     f32x4 s0 = {0, 0, 0, 0}, s1 = {0, 0, 0, 0};
     f32x4 dp0 = {0, 0, 0, 0}, dp1 = {0, 0, 0, 0};
 #pragma unroll
     for (int sl = 0; sl < DTILES / 2; ++sl) {
-      const int c0 = 32 * sl + 8 * (lane >> 4);
+      const int c0 = 32 * sl + 8 * g;
       bf16x8 qa = load_frag_rm<DTILES>(q_rm, lane & 15, c0);
       bf16x8 qa1 = load_frag_rm<DTILES>(q_rm, 16 + (lane & 15), c0);
       s0 = mfma_bf16(qa, kb_[sl], s0);
@@ -499,27 +489,28 @@ __global__ void attn_bwd_dkv_k(const ushort* __restrict__ dout,
     f32x4 p0, p1, ds0, ds1;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
+      // roles swapped: this lane's key krow against the tile's queries
       const int qa0 = q0 + 4 * g + r, qa1 = qa0 + 16;
-      const bool v0 = (qa0 >= krow && qa0 < seq && kv_ok);
-      const bool v1 = (qa1 >= krow && qa1 < seq && kv_ok);
-      const float l0 = lse[bhid * seq + (v0 ? qa0 : 0)] * LOG2E;
-      const float l1 = lse[bhid * seq + (v1 ? qa1 : 0)] * LOG2E;
-      p0[r] = v0 ? __builtin_exp2f(s0[r] * sc2 - l0) : 0.f;
-      p1[r] = v1 ? __builtin_exp2f(s1[r] * sc2 - l1) : 0.f;
-      const float d0 = delta[bhid * seq + ((qa0 < seq) ? qa0 : 0)];
-      const float d1 = delta[bhid * seq + ((qa1 < seq) ? qa1 : 0)];
-      if (thr) {
+      const bool v0 = qa0 < seq && attn_visible(qa0, krow, kvl);
+      const bool v1 = qa1 < seq && attn_visible(qa1, krow, kvl);
+      const float l0 = lse[c.bhid * seq + (v0 ? qa0 : 0)] * LOG2E;
+      const float l1 = lse[c.bhid * seq + (v1 ? qa1 : 0)] * LOG2E;
+      p0[r] = v0 ? __builtin_exp2f(s0[r] * c.sc2 - l0) : 0.f;
+      p1[r] = v1 ? __builtin_exp2f(s1[r] * c.sc2 - l1) : 0.f;
+      const float d0 = delta[c.bhid * seq + ((qa0 < seq) ? qa0 : 0)];
+      const float d1 = delta[c.bhid * seq + ((qa1 < seq) ? qa1 : 0)];
+      if (c.thr) {
         // element (q, k=krow): slice krow&3 of hash(q, krow>>2) — the
         // transposed view of the SAME per-(b,h,q,k) draw the fwd/dq
         // kernels take; dV uses the dropped P, dK the dropout-gated dS
         const uint64_t hk0 =
-            rng_attn_hash(drop_s2, uint32_t(qa0), uint32_t(krow) >> 2);
+            rng_attn_hash(c.drop_s2, uint32_t(qa0), uint32_t(krow) >> 2);
         const uint64_t hk1 =
-            rng_attn_hash(drop_s2, uint32_t(qa1), uint32_t(krow) >> 2);
+            rng_attn_hash(c.drop_s2, uint32_t(qa1), uint32_t(krow) >> 2);
         const float m0 =
-            rng_keep(hk0, krow & 3, thr) ? geo.drop.inv_keep : 0.f;
+            rng_keep(hk0, krow & 3, c.thr) ? geo.drop.inv_keep : 0.f;
         const float m1 =
-            rng_keep(hk1, krow & 3, thr) ? geo.drop.inv_keep : 0.f;
+            rng_keep(hk1, krow & 3, c.thr) ? geo.drop.inv_keep : 0.f;
         // dS = A ⊙ (M/(1-p)·dp − delta); dV gets the dropped P = A·M/(1-p)
         ds0[r] = p0[r] * (m0 * dp0[r] - d0);
         ds1[r] = p1[r] * (m1 * dp1[r] - d1);
@@ -541,26 +532,24 @@ __global__ void attn_bwd_dkv_k(const ushort* __restrict__ dout,
     }
   }
   if (!live) return;
-  constexpr int D = 16 * DTILES;
-#pragma unroll
-  for (int t = 0; t < DTILES; ++t)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int orow = kv0 + 4 * g + r;
-      if (orow >= seq) continue;
-      const int col = 16 * t + (lane & 15);
-      if (ATOMIC) {
-        // fp32 accumulation across the grp q-heads sharing this kv head
-        int64_t off = ((int64_t(b) * (geo.H / geo.grp) + hk) * seq + orow) * D + col;
-        atomicAdd(dk32 + off, acck[t][r] * geo.scale);
-        atomicAdd(dv32 + off, accv[t][r]);
-      } else {
-        ushort* dkp = dk + b * geo.gkb + hk * geo.gkh;
-        ushort* dvp = dv + b * geo.gkb + hk * geo.gkh;
-        dkp[int64_t(orow) * geo.gks + col] = f2bf(acck[t][r] * geo.scale);
-        dvp[int64_t(orow) * geo.gks + col] = f2bf(accv[t][r]);
-      }
+  // One walk for both outputs: storing dk and dv in two passes costs the
+  // head-dim-128 instantiation 16 more bytes of spill.
+  for_acc_rows<DTILES>(kv0, seq, lane, [&](int t, int r, int row, int col) {
+    if (ATOMIC) {
+      // fp32 accumulation across the grp q-heads sharing this kv head,
+      // into contiguous [B,Hk,S,D]
+      const int64_t off =
+          ((int64_t(c.b) * (geo.H / geo.grp) + c.hk) * seq + row) *
+              (16 * DTILES) + col;
+      atomicAdd(dk32 + off, acck[t][r] * geo.scale);
+      atomicAdd(dv32 + off, accv[t][r]);
+    } else {
+      ushort* dkp = dk + c.b * geo.dkv.batch + c.hk * geo.dkv.head;
+      ushort* dvp = dv + c.b * geo.dkv.batch + c.hk * geo.dkv.head;
+      dkp[int64_t(row) * geo.dkv.seq + col] = f2bf(acck[t][r] * geo.scale);
+      dvp[int64_t(row) * geo.dkv.seq + col] = f2bf(accv[t][r]);
     }
+  });
 }
 
 // ---------------- decode (KV-cache serving path) ----------------
@@ -727,7 +716,6 @@ __global__ void mfma_probe16_k(const ushort* A, const ushort* B, float* D) {
 
 __global__ void mfma_probe32_k(const ushort* A, const ushort* B, float* D) {
   const int lane = threadIdx.x & 63;
-  typedef __attribute__((ext_vector_type(16))) float f32x16_t;
   bf16x8 a, b;
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
@@ -737,7 +725,7 @@ __global__ void mfma_probe32_k(const ushort* A, const ushort* B, float* D) {
     a[j] = ca.v;
     b[j] = cb.v;
   }
-  f32x16_t c = {};
+  f32x16 c = {};
   c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
@@ -746,28 +734,40 @@ __global__ void mfma_probe32_k(const ushort* A, const ushort* B, float* D) {
   }
 }
 
+// ---- head-dim dispatch ------------------------------------------------------
+// f(std::integral_constant<int, DTILES>) for hd = 16 * DTILES. The bindings
+// reject other head dims before any launch. HD32: whether the kernel family
+// is instantiated for head dim 32 (decode is not).
+template <bool HD32 = true, class F>
+void for_head_dim(int hd, F f) {
+  if (hd == 64) f(std::integral_constant<int, 4>{});
+  else if (hd == 128) f(std::integral_constant<int, 8>{});
+  else if constexpr (HD32)
+    if (hd == 32) f(std::integral_constant<int, 2>{});
+}
+
+dim3 attn_grid(const AttnGeom& geo) {
+  return dim3((geo.seq + 63) / 64, int64_t(geo.B) * geo.H);
+}
+
 }  // namespace
 
 void launch_attn_fwd(const bf16_t* q, const bf16_t* k, const bf16_t* v,
                      bf16_t* o, float* lse, const AttnGeom& geo,
                      hipStream_t s) {
-  dim3 grid((geo.seq + 63) / 64, int64_t(geo.B) * geo.H);
-  const int hd = geo.hd;
-  if (hd == 64) attn_fwd_k<4><<<grid, 256, 0, s>>>(q, k, v, o, lse, geo);
-  else if (hd == 128) attn_fwd_k<8><<<grid, 256, 0, s>>>(q, k, v, o, lse, geo);
-  else if (hd == 32) attn_fwd_k<2><<<grid, 256, 0, s>>>(q, k, v, o, lse, geo);
+  for_head_dim(geo.hd, [&](auto dt) {
+    attn_fwd_k<dt()><<<attn_grid(geo), 256, 0, s>>>(q, k, v, o, lse, geo);
+  });
 }
 
 void launch_attn_bwd_dq(const bf16_t* dout, const bf16_t* q, const bf16_t* k,
-                        const bf16_t* v, const bf16_t* o, int64_t ob2,
-                        int64_t oh2, int64_t os2, const float* lse,
+                        const bf16_t* v, const bf16_t* o, const float* lse,
                         float* delta, bf16_t* dq, const AttnGeom& geo,
                         hipStream_t s) {
-  dim3 grid((geo.seq + 63) / 64, int64_t(geo.B) * geo.H);
-  const int hd = geo.hd;
-  if (hd == 64) attn_bwd_dq_k<4><<<grid, 256, 0, s>>>(dout, q, k, v, o, ob2, oh2, os2, lse, delta, dq, geo);
-  else if (hd == 128) attn_bwd_dq_k<8><<<grid, 256, 0, s>>>(dout, q, k, v, o, ob2, oh2, os2, lse, delta, dq, geo);
-  else if (hd == 32) attn_bwd_dq_k<2><<<grid, 256, 0, s>>>(dout, q, k, v, o, ob2, oh2, os2, lse, delta, dq, geo);
+  for_head_dim(geo.hd, [&](auto dt) {
+    attn_bwd_dq_k<dt()><<<attn_grid(geo), 256, 0, s>>>(dout, q, k, v, o, lse,
+                                                       delta, dq, geo);
+  });
 }
 
 void launch_attn_bwd_dkv(const bf16_t* dout, const bf16_t* q,
@@ -775,25 +775,13 @@ void launch_attn_bwd_dkv(const bf16_t* dout, const bf16_t* q,
                          const float* delta, float* dk32, float* dv32,
                          bf16_t* dk, bf16_t* dv, const AttnGeom& geo,
                          hipStream_t s) {
-  dim3 grid((geo.seq + 63) / 64, int64_t(geo.B) * geo.H);
-  const int hd = geo.hd;
-  const bool at = geo.grp > 1;  // GQA folds heads via fp32 atomics;
-                                // grp==1 stores bf16 directly
-#define DKV(D_)                                                              \
-  do {                                                                       \
-    if (at)                                                                  \
-      attn_bwd_dkv_k<D_, true><<<grid, 256, 0, s>>>(dout, q, k, v, lse,      \
-                                                    delta, dk32, dv32, dk,   \
-                                                    dv, geo);                \
-    else                                                                     \
-      attn_bwd_dkv_k<D_, false><<<grid, 256, 0, s>>>(dout, q, k, v, lse,     \
-                                                     delta, dk32, dv32, dk,  \
-                                                     dv, geo);               \
-  } while (0)
-  if (hd == 64) DKV(4);
-  else if (hd == 128) DKV(8);
-  else if (hd == 32) DKV(2);
-#undef DKV
+  for_head_dim(geo.hd, [&](auto dt) {
+    // GQA folds heads via fp32 atomics; grp==1 stores bf16 directly
+    auto kern = geo.grp > 1 ? attn_bwd_dkv_k<dt(), true>
+                            : attn_bwd_dkv_k<dt(), false>;
+    kern<<<attn_grid(geo), 256, 0, s>>>(dout, q, k, v, lse, delta, dk32,
+                                        dv32, dk, dv, geo);
+  });
 }
 
 void launch_mfma_probe_16(const bf16_t* A, const bf16_t* B, float* D,
@@ -809,11 +797,9 @@ void launch_attn_decode(const bf16_t* q, const bf16_t* kc, const bf16_t* vc,
                         bf16_t* o, int B, int H, int grp, int kvlen,
                         const int* len_p, int hd, int64_t cb, int64_t ch,
                         float scale, hipStream_t s) {
-  const int grid = B * H;   // block per (b, h); 4 waves split the cache
-  if (hd == 64)
-    attn_decode_k<4><<<grid, 256, 0, s>>>(q, kc, vc, o, B, H, grp, kvlen,
-                                          len_p, cb, ch, scale);
-  else if (hd == 128)
-    attn_decode_k<8><<<grid, 256, 0, s>>>(q, kc, vc, o, B, H, grp, kvlen,
-                                          len_p, cb, ch, scale);
+  // block per (b, h); 4 waves split the cache
+  for_head_dim<false>(hd, [&](auto dt) {
+    attn_decode_k<dt()><<<B * H, 256, 0, s>>>(q, kc, vc, o, B, H, grp, kvlen,
+                                              len_p, cb, ch, scale);
+  });
 }

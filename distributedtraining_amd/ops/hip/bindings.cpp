@@ -582,6 +582,16 @@ static void set_mask_drop(AttnGeom& g, const Tensor& kvlen, const Tensor& rng,
   g.drop = drop_params(rng, site, p);
 }
 
+// (batch, head, seq) strides of a [B,H,S,D] view and of a [B,S,H,D] tensor
+static AttnStride strides_bhsd(const Tensor& t) {
+  return {t.stride(0), t.stride(1), t.stride(2)};
+}
+static AttnStride strides_bshd(const Tensor& t) {
+  return {t.stride(0), t.stride(2), t.stride(1)};
+}
+
+// q/k/v/dout: [B,H(,Hk),S,D] views; o_bshd: [B,S,H,D]. dout may be undefined
+// (forward); the backward adds its output strides itself.
 static AttnGeom make_geom(const Tensor& q, const Tensor& k, const Tensor& v,
                           const Tensor& o_bshd, const Tensor& dout,
                           double scale) {
@@ -592,14 +602,9 @@ static AttnGeom make_geom(const Tensor& q, const Tensor& k, const Tensor& v,
   TORCH_CHECK(g.H % hk == 0, "H must be a multiple of H_kv");
   g.grp = g.H / hk;
   g.scale = float(scale);
-  g.qb = q.stride(0); g.qh = q.stride(1); g.qs = q.stride(2);
-  g.kb = k.stride(0); g.kh = k.stride(1); g.ks = k.stride(2);
-  g.vb = v.stride(0); g.vh = v.stride(1); g.vs = v.stride(2);
-  // o_bshd is [B,S,H,D]: strides (batch, head, seq) = (0th, 2nd, 1st)
-  g.ob = o_bshd.stride(0); g.oh = o_bshd.stride(2); g.os_ = o_bshd.stride(1);
-  if (dout.defined()) {
-    g.db_ = dout.stride(0); g.dh = dout.stride(1); g.ds = dout.stride(2);
-  }
+  g.q = strides_bhsd(q); g.k = strides_bhsd(k); g.v = strides_bhsd(v);
+  g.o = strides_bshd(o_bshd);
+  if (dout.defined()) g.dout = strides_bhsd(dout);
   return g;
 }
 
@@ -619,41 +624,63 @@ std::vector<Tensor> attn_fwd(Tensor q, Tensor k, Tensor v, double scale,
   return {o, lse};  // caller views o as [B,H,S,D] via permute(0,2,1,3)
 }
 
+// The backward both entry points share: delta alloc -> dQ -> dK/dV.
+// dq_v: [B,S,H,D] destination view (contiguous D), always written.
+// grp == 1: dk/dv are stored straight into the [B,S,Hk,D] views dk_v/dv_v.
+// GQA: the q heads fold into zeroed fp32 [B,Hk,S,D] buffers with atomics;
+// dk_v/dv_v are not touched and the buffers are handed back for the caller
+// to cast into place.
+static std::pair<Tensor, Tensor> attn_bwd_into(
+    const Tensor& dout, const Tensor& q, const Tensor& k, const Tensor& v,
+    const Tensor& o_bshd, const Tensor& lse, double scale,
+    const Tensor& kvlen, const Tensor& rng, int64_t site, double p,
+    Tensor dq_v, Tensor dk_v, Tensor dv_v) {
+  check_attn_view(dout, "dout");
+  TORCH_CHECK(dq_v.stride(3) == 1, "dq view needs contiguous head_dim");
+  const int64_t B = q.size(0), H = q.size(1), S = q.size(2);
+  AttnGeom geo = make_geom(q, k, v, o_bshd, dout, scale);
+  geo.dq = strides_bshd(dq_v);
+  set_mask_drop(geo, kvlen, rng, site, p, B);
+  auto delta = torch::empty({B * H, S}, lse.options());
+  launch_attn_bwd_dq(bfp(dout), bfp(q), bfp(k), bfp(v), bfp(o_bshd),
+                     lse.data_ptr<float>(), delta.data_ptr<float>(),
+                     bfp_mut(dq_v), geo, stream());
+  Tensor dk32, dv32;
+  if (geo.grp == 1) {
+    TORCH_CHECK(dk_v.stride(3) == 1 && dk_v.strides() == dv_v.strides(),
+                "dk/dv views need contiguous head_dim and equal strides");
+    geo.dkv = strides_bshd(dk_v);
+  } else {
+    dk32 = torch::zeros({B, k.size(1), S, q.size(3)},
+                        q.options().dtype(torch::kFloat32));
+    dv32 = torch::zeros_like(dk32);
+  }
+  launch_attn_bwd_dkv(bfp(dout), bfp(q), bfp(k), bfp(v),
+                      lse.data_ptr<float>(), delta.data_ptr<float>(),
+                      geo.grp == 1 ? nullptr : dk32.data_ptr<float>(),
+                      geo.grp == 1 ? nullptr : dv32.data_ptr<float>(),
+                      geo.grp == 1 ? bfp_mut(dk_v) : nullptr,
+                      geo.grp == 1 ? bfp_mut(dv_v) : nullptr, geo, stream());
+  return {dk32, dv32};
+}
+
+// Returns dq [B,S,H,D] and dk/dv as [B,Hk,S,D]: permuted views of
+// [B,S,Hk,D] stores, or with GQA the contiguous cast of the fp32 buffers.
 std::vector<Tensor> attn_bwd(Tensor dout, Tensor q, Tensor k, Tensor v,
                              Tensor o_bshd, Tensor lse, double scale,
                              Tensor kvlen, Tensor rng, int64_t site,
                              double p) {
-  check_attn_view(dout, "dout");
-  const int64_t B = q.size(0), H = q.size(1), S = q.size(2);
-  const int hd = int(q.size(3));
+  const int64_t B = q.size(0), H = q.size(1), S = q.size(2), hd = q.size(3);
   const int64_t Hk = k.size(1);
-  AttnGeom geo = make_geom(q, k, v, o_bshd, dout, scale);
-  set_mask_drop(geo, kvlen, rng, site, p, B);
-  auto delta = torch::empty({B * H, S}, lse.options());
   auto dq = torch::empty({B, S, H, hd}, q.options());
-  launch_attn_bwd_dq(bfp(dout), bfp(q), bfp(k), bfp(v), bfp(o_bshd),
-                     o_bshd.stride(0), o_bshd.stride(2), o_bshd.stride(1),
-                     lse.data_ptr<float>(), delta.data_ptr<float>(),
-                     bfp_mut(dq), geo, stream());
-  if (geo.grp == 1) {
-    // direct bf16 store into [B,S,Hk,D]; caller permutes to [B,Hk,S,D]
-    auto dk = torch::empty({B, S, Hk, hd}, q.options());
-    auto dv = torch::empty({B, S, Hk, hd}, q.options());
-    geo.gkb = dk.stride(0); geo.gkh = dk.stride(2); geo.gks = dk.stride(1);
-    launch_attn_bwd_dkv(bfp(dout), bfp(q), bfp(k), bfp(v),
-                        lse.data_ptr<float>(), delta.data_ptr<float>(),
-                        nullptr, nullptr, bfp_mut(dk), bfp_mut(dv), geo,
-                        stream());
-    return {dq, dk.permute({0, 2, 1, 3}), dv.permute({0, 2, 1, 3})};
+  Tensor dk, dv;
+  if (H == Hk) {
+    dk = torch::empty({B, S, Hk, hd}, q.options());
+    dv = torch::empty_like(dk);
   }
-  // GQA: accumulate in fp32 [B,Hk,S,D] (q heads fold in), then cast
-  auto dk32 = torch::zeros({B, Hk, S, hd},
-                           q.options().dtype(torch::kFloat32));
-  auto dv32 = torch::zeros_like(dk32);
-  launch_attn_bwd_dkv(bfp(dout), bfp(q), bfp(k), bfp(v),
-                      lse.data_ptr<float>(), delta.data_ptr<float>(),
-                      dk32.data_ptr<float>(), dv32.data_ptr<float>(),
-                      nullptr, nullptr, geo, stream());
+  auto [dk32, dv32] = attn_bwd_into(dout, q, k, v, o_bshd, lse, scale, kvlen,
+                                    rng, site, p, dq, dk, dv);
+  if (H == Hk) return {dq, dk.permute({0, 2, 1, 3}), dv.permute({0, 2, 1, 3})};
   return {dq, dk32.to(torch::kBFloat16), dv32.to(torch::kBFloat16)};
 }
 
@@ -664,38 +691,11 @@ void attn_bwd_packed(Tensor dout, Tensor q, Tensor k, Tensor v,
                      Tensor o_bshd, Tensor lse, double scale, Tensor dq_v,
                      Tensor dk_v, Tensor dv_v, Tensor kvlen, Tensor rng,
                      int64_t site, double p) {
-  check_attn_view(dout, "dout");
-  TORCH_CHECK(dq_v.stride(3) == 1 && dk_v.stride(3) == 1 &&
-              dv_v.stride(3) == 1, "dqkv views need contiguous head_dim");
-  const int64_t B = q.size(0), H = q.size(1), S = q.size(2);
-  const int hd = int(q.size(3));
-  const int64_t Hk = k.size(1);
-  AttnGeom geo = make_geom(q, k, v, o_bshd, dout, scale);
-  set_mask_drop(geo, kvlen, rng, site, p, B);
-  auto delta = torch::empty({B * H, S}, lse.options());
-  AttnGeom gq = geo;  // dq_v is [B,S,H,D]: (batch, head, seq) strides
-  gq.ob = dq_v.stride(0); gq.oh = dq_v.stride(2); gq.os_ = dq_v.stride(1);
-  launch_attn_bwd_dq(bfp(dout), bfp(q), bfp(k), bfp(v), bfp(o_bshd),
-                     o_bshd.stride(0), o_bshd.stride(2), o_bshd.stride(1),
-                     lse.data_ptr<float>(), delta.data_ptr<float>(),
-                     bfp_mut(dq_v), gq, stream());
-  if (geo.grp == 1) {
-    geo.gkb = dk_v.stride(0); geo.gkh = dk_v.stride(2);
-    geo.gks = dk_v.stride(1);
-    launch_attn_bwd_dkv(bfp(dout), bfp(q), bfp(k), bfp(v),
-                        lse.data_ptr<float>(), delta.data_ptr<float>(),
-                        nullptr, nullptr, bfp_mut(dk_v), bfp_mut(dv_v), geo,
-                        stream());
-    return;
-  }
-  // GQA: fp32 accumulation (q-head fold-in), then cast into the views
-  auto dk32 = torch::zeros({B, Hk, S, hd},
-                           q.options().dtype(torch::kFloat32));
-  auto dv32 = torch::zeros_like(dk32);
-  launch_attn_bwd_dkv(bfp(dout), bfp(q), bfp(k), bfp(v),
-                      lse.data_ptr<float>(), delta.data_ptr<float>(),
-                      dk32.data_ptr<float>(), dv32.data_ptr<float>(),
-                      nullptr, nullptr, geo, stream());
+  TORCH_CHECK(dk_v.stride(3) == 1 && dv_v.stride(3) == 1,
+              "dqkv views need contiguous head_dim");
+  auto [dk32, dv32] = attn_bwd_into(dout, q, k, v, o_bshd, lse, scale, kvlen,
+                                    rng, site, p, dq_v, dk_v, dv_v);
+  if (!dk32.defined()) return;
   dk_v.copy_(dk32.permute({0, 2, 1, 3}));
   dv_v.copy_(dv32.permute({0, 2, 1, 3}));
 }

@@ -31,6 +31,18 @@ DEV ushort f2bf(float f) {
   return x.s;
 }
 
+// ---- MFMA operands ---------------------------------------------------------
+// 16 B of memory (8 bf16 loaded as s16x8) reinterpreted as an MFMA operand
+DEV bf16x8 as_bf16x8(s16x8 v) {
+  union { s16x8 s; bf16x8 b; } u;
+  u.s = v;
+  return u.b;
+}
+// D[16,16] = A[16,32] x B[32,16] + C; lane layouts: attention.hip header
+DEV f32x4 mfma_bf16(bf16x8 a, bf16x8 b, f32x4 c) {
+  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
+}
+
 // ---- fast transcendentals (exp2/log2 are single hardware instructions) ----
 #define LOG2E 1.4426950408889634f
 #define LN2 0.6931471805599453f

@@ -238,18 +238,16 @@ void launch_rope(const bf16_t* x, const float* cos_t, const float* sin_t,
                  const int* pos_p, hipStream_t s);
 
 // ---- attention ------------------------------------------------------------
-// Strided geometry: q/k/v/o/dout are [B,H,S,D]-shaped views with arbitrary
-// batch/head/seq strides (innermost D contiguous); kv tensors have H/grp
-// heads (GQA). lse/delta are [B*H, S] fp32 contiguous.
+// Strided geometry: every tensor is addressed as (batch, head, seq) strides
+// over contiguous head_dim rows, whatever its memory order; kv tensors have
+// H/grp heads (GQA). lse/delta are [B*H, S] fp32 contiguous.
+struct AttnStride { int64_t batch, head, seq; };
 struct AttnGeom {
   int B, H, grp, seq, hd;
   float scale;
-  int64_t qb, qh, qs;      // q strides (batch, head, seq)
-  int64_t kb, kh, ks;      // k strides
-  int64_t vb, vh, vs;      // v strides
-  int64_t ob, oh, os_;     // o (and dq) strides
-  int64_t db_, dh, ds;     // dout strides
-  int64_t gkb, gkh, gks;   // dk/dv output strides (grp==1 direct-store path)
+  AttnStride q, k, v, o;   // forward operands and output
+  AttnStride dout, dq;     // backward: incoming and query gradient
+  AttnStride dkv;          // dk and dv of the direct-store path (grp == 1)
   // padding mask (reference attention_mask, right-padded batches:
   // training_manager.py:380-385): key j of batch row b is valid iff
   // j < kvlen[b]. null = no mask (all keys valid).
@@ -260,13 +258,13 @@ struct AttnGeom {
 void launch_attn_fwd(const bf16_t* q, const bf16_t* k, const bf16_t* v,
                      bf16_t* o, float* lse, const AttnGeom& geo,
                      hipStream_t s);
-// computes delta[q]=rowsum(dO*O) itself (o + its strides passed
-// explicitly: geo.ob may be overridden for the packed dq output)
+// also computes delta[q] = rowsum(dO * O) for the dkv kernel
 void launch_attn_bwd_dq(const bf16_t* dout, const bf16_t* q, const bf16_t* k,
-                        const bf16_t* v, const bf16_t* o, int64_t ob2,
-                        int64_t oh2, int64_t os2, const float* lse,
+                        const bf16_t* v, const bf16_t* o, const float* lse,
                         float* delta, bf16_t* dq, const AttnGeom& geo,
                         hipStream_t s);
+// grp > 1: fp32 atomics into zeroed contiguous [B,Hk,S,D] dk32/dv32;
+// grp == 1: bf16 stores into dk/dv with the dkv strides
 void launch_attn_bwd_dkv(const bf16_t* dout, const bf16_t* q,
                          const bf16_t* k, const bf16_t* v, const float* lse,
                          const float* delta, float* dk32, float* dv32,

@@ -57,17 +57,11 @@ constexpr int HL_BUF = 2 * HL_TILE;        // W tile + x tile
 
 static_assert(HL_BM == 128 && HL_BN == 128, "wave layout assumes 128x128");
 
-DEV f32x4 hl_mfma(bf16x8 a, bf16x8 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-
 // element offset of 16 B chunk c (0..7) of row r in a swizzled [128][64] tile
 DEV int hl_off(int r, int c) { return r * HL_BK + ((c ^ ((r >> 1) & 7)) << 3); }
 
 DEV bf16x8 hl_frag(const ushort* tile, int r, int c) {
-  union { s16x8 s; bf16x8 b; } u;
-  u.s = *reinterpret_cast<const s16x8*>(tile + hl_off(r, c));
-  return u.b;
+  return as_bf16x8(*reinterpret_cast<const s16x8*>(tile + hl_off(r, c)));
 }
 
 // (m, s) <- (m, s) (+) (m2, s2) in exp2 units. An all -inf side (a lane that
@@ -172,7 +166,7 @@ __global__ __launch_bounds__(HL_THREADS, 2) void head_loss_k(
 #pragma unroll
       for (int i = 0; i < 4; ++i)
 #pragma unroll
-        for (int n = 0; n < 4; ++n) acc[i][n] = hl_mfma(a[i], b[n], acc[i][n]);
+        for (int n = 0; n < 4; ++n) acc[i][n] = mfma_bf16(a[i], b[n], acc[i][n]);
     }
 
     if (++cks == nk) {

@@ -191,7 +191,11 @@ def test_swiglu():
                                          (1, 2, 2, 512, 64),
                                          (2, 2, 2, 128, 128),
                                          (1, 1, 1, 48, 32),
-                                         (2, 8, 2, 64, 128)])  # GQA
+                                         (2, 8, 2, 64, 128),   # GQA
+                                         # ragged: second 64-row block with
+                                         # one partly live wave, three dead
+                                         (2, 3, 3, 70, 64),
+                                         (1, 2, 2, 70, 32)])
 def test_attention_fwd_bwd(B, H, Hkv, S, D):
     """Through the autograd wrapper (as the models call it), strided
     [B,H,S,D] views included."""
@@ -849,7 +853,8 @@ def test_attention_dropout_fwd_bwd(B, H, Hkv, S, D, p):
 
 
 @pytest.mark.parametrize("B,H,Hkv,S,D,p", [(3, 2, 2, 64, 64, 0.1),
-                                           (2, 4, 2, 96, 128, 0.25)])
+                                           (2, 4, 2, 96, 128, 0.25),
+                                           (2, 4, 1, 70, 128, 0.25)])
 def test_attention_masked_dropout_fwd_bwd(B, H, Hkv, S, D, p):
     """kvlen padding mask AND attention-prob dropout TOGETHER (the actual
     training configuration on ragged real-text batches): the dropout draws
@@ -896,6 +901,93 @@ def test_attention_masked_dropout_fwd_bwd(B, H, Hkv, S, D, p):
         L = int(kvlen[b])
         assert torch.all(k.grad[b, :, L:] == 0)
         assert torch.all(v.grad[b, :, L:] == 0)
+
+
+def _packed_views(t, H, Hk, D):
+    """q/k/v [B,heads,S,D] views of a packed [B,S,(H+2Hk)D] tensor."""
+    B, S, _ = t.shape
+    E, kvd = H * D, Hk * D
+    return (t[..., :E].view(B, S, H, D).transpose(1, 2),
+            t[..., E:E + kvd].view(B, S, Hk, D).transpose(1, 2),
+            t[..., E + kvd:].view(B, S, Hk, D).transpose(1, 2))
+
+
+@pytest.mark.parametrize("B,H,Hk,S,D,p", [(2, 4, 2, 70, 64, 0.25),
+                                          (2, 2, 2, 48, 32, 0.1)])
+def test_qkv_attention_packed_masked_dropout(B, H, Hk, S, D, p):
+    """The packed entry point with kvlen mask AND dropout (the GPT-2
+    training configuration) against the host gold on the sliced views."""
+    from distributedtraining_amd import ops
+    from distributedtraining_amd.ops import droprng
+    scale = 1.0 / math.sqrt(D)
+    torch.manual_seed(60)
+    site = 13
+    kvlen = torch.randint(1, S + 1, (B,), dtype=torch.int32)
+    kvlen[0] = S
+    kvlen[-1] = 1
+    qkv = _rand_bf16(B, S, (H + 2 * Hk) * D, seed=61).requires_grad_(True)
+    droprng.counter(DEV).fill_(77)
+    o = ops.qkv_attention(qkv, H, Hk, kvlen=kvlen.to(DEV), p_drop=p,
+                          site=site)
+    qf = qkv.detach().cpu().float().requires_grad_(True)
+    ref = _attn_ref_cpu(*_packed_views(qf, H, Hk, D), scale, kvlen,
+                        p_drop=p, site=site, ctr=77)
+    ref = ref.transpose(1, 2).reshape(B, S, H * D)
+    torch.testing.assert_close(o.float().cpu(), ref.detach(), rtol=4e-2,
+                               atol=4e-2)
+
+    do = _rand_bf16(B, S, H * D, seed=62)
+    qmask = (torch.arange(S)[None, :] < kvlen[:, None].long()) \
+        .to(DEV).view(B, S, 1)
+    do = (do * qmask).to(torch.bfloat16)
+    o.backward(do)
+    ref.backward(do.float().cpu())
+    gq, gk, gv = _packed_views(qkv.grad.float().cpu(), H, Hk, D)
+    rq, rk, rv = _packed_views(qf.grad, H, Hk, D)
+    torch.testing.assert_close(gq, rq, rtol=6e-2, atol=6e-2)
+    torch.testing.assert_close(gk, rk, rtol=6e-2, atol=8e-2)
+    torch.testing.assert_close(gv, rv, rtol=6e-2, atol=6e-2)
+    for b in range(B):
+        L = int(kvlen[b])
+        assert torch.all(gk[b, :, L:] == 0)
+        assert torch.all(gv[b, :, L:] == 0)
+
+
+@pytest.mark.parametrize("B,H,Hk,S,D", [(2, 4, 4, 70, 64), (2, 4, 2, 70, 64)])
+def test_qkv_attention_packed_equals_unpacked(B, H, Hk, S, D):
+    """causal_attention on the views of a packed buffer and qkv_attention
+    on the buffer are one computation: o and dq bit-equal; dk/dv bit-equal
+    without GQA (with it they fold through float atomics)."""
+    from distributedtraining_amd import ops
+    from distributedtraining_amd.ops import droprng
+    p, site = 0.25, 17
+    kvlen = torch.tensor([S] + [S - 29] * (B - 1), dtype=torch.int32,
+                         device=DEV)
+    qkv = _rand_bf16(B, S, (H + 2 * Hk) * D, seed=71)
+    do = _rand_bf16(B, S, H * D, seed=72)
+
+    packed = qkv.clone().requires_grad_(True)
+    droprng.counter(DEV).fill_(123)
+    o_p = ops.qkv_attention(packed, H, Hk, kvlen=kvlen, p_drop=p, site=site)
+    o_p.backward(do)
+
+    q, k, v = (t.detach().requires_grad_(True)
+               for t in _packed_views(qkv, H, Hk, D))
+    droprng.counter(DEV).fill_(123)
+    o_u = ops.causal_attention(q, k, v, kvlen=kvlen, p_drop=p, site=site)
+    o_u.backward(do.view(B, S, H, D).transpose(1, 2))
+
+    assert torch.equal(o_p, o_u.transpose(1, 2).reshape(B, S, H * D))
+    gq, gk, gv = _packed_views(packed.grad, H, Hk, D)
+    assert torch.equal(gq, q.grad)
+    if H == Hk:
+        assert torch.equal(gk, k.grad)
+        assert torch.equal(gv, v.grad)
+    else:
+        torch.testing.assert_close(gk.float(), k.grad.float(), rtol=6e-2,
+                                   atol=8e-2)
+        torch.testing.assert_close(gv.float(), v.grad.float(), rtol=6e-2,
+                                   atol=6e-2)
 
 
 def test_dropout_kernel_matches_host_gold():

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
-"""SHA-256 of every output of the norm, dropout and attention entry points
-on seeded inputs with the dropout counter pinned — a bit-for-bit fingerprint
-for refactors that must not change arithmetic.
+"""SHA-256 of every output of the norm, dropout, attention and decode entry
+points on seeded inputs with the dropout counter pinned — a bit-for-bit
+fingerprint for refactors that must not change arithmetic.
 
 Each case runs twice; an output whose bytes differ between the two runs
 (atomically reduced dγ/dβ, GQA dk/dv) is listed as ``unstable`` and left out
@@ -94,11 +94,24 @@ def attn_case(B, H, Hk, S, D):
             "attn_bwd_packed.dk": pk, "attn_bwd_packed.dv": pv}
 
 
+def decode_case(B, H, Hk, L, D):
+    q = rand(B, H, D, seed=10)
+    kc, vc = rand(B, Hk, L + 7, D, seed=11), rand(B, Hk, L + 7, D, seed=12)
+    return {"attn_decode.o": m.attn_decode(
+        q, kc, vc, L, D ** -0.5,
+        torch.empty(0, dtype=torch.int32, device=DEV))}
+
+
 CASES = [(f"norm[{r}x{c},{'res+drop' if f else 'plain'}]", norm_case,
           (r, c, f)) for r, c in ((128, 768), (33, 2560)) for f in (0, 1)]
 CASES.append(("dropout[100003]", dropout_case, (100_003,)))
 CASES += [(f"attn[{'x'.join(map(str, g))}]", attn_case, g)
-          for g in ((2, 4, 4, 96, 64), (2, 8, 2, 96, 64))]
+          for g in ((2, 4, 4, 96, 64), (2, 8, 2, 96, 64),
+                    # S = 70: a second 64-row block, one wave partly live;
+                    # all three head dims, direct and atomic dk/dv at 128
+                    (2, 2, 2, 70, 32), (2, 4, 1, 70, 128), (2, 3, 3, 70, 64))]
+CASES += [(f"decode[{'x'.join(map(str, g))}]", decode_case, g)
+          for g in ((2, 4, 2, 130, 64), (1, 4, 4, 130, 128))]
 
 
 def digests(fn, a):
