@@ -172,7 +172,8 @@ class GPT2LM(nn.Module):
         want_logits = bool(return_logits) or not self.training
         loss, logits = ops.lm_head_ce(x[:, :-1, :].contiguous(), self.wte,
                                       tgt.contiguous().view(-1),
-                                      need_logits=want_logits)
+                                      need_logits=want_logits,
+                                      overwrite_logits=not want_logits)
         return CausalLMOutput(
             loss=loss,
             logits=(logits.view(B, S - 1, self.cfg.vocab_size)

@@ -172,7 +172,8 @@ class LlamaLM(nn.Module):
         loss, logits = ops.lm_head_ce(x[:, :-1, :].contiguous(),
                                       self._head(),
                                       tgt.contiguous().view(-1),
-                                      need_logits=want_logits)
+                                      need_logits=want_logits,
+                                      overwrite_logits=not want_logits)
         return CausalLMOutput(
             loss=loss,
             logits=(logits.view(B, S - 1, self.cfg.vocab_size)

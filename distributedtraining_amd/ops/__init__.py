@@ -727,6 +727,13 @@ def cross_entropy_loss(logits: torch.Tensor, targets: torch.Tensor,
 _CE_PIPE = _os.environ.get("DTA_CE_PIPELINE", "0") == "1"
 _CE_TT = int(_os.environ.get("DTA_CE_TT", "8192"))
 _CE_VC = int(_os.environ.get("DTA_CE_VC", "4224"))
+# One-pass CE for training (no second 6.5 GB logits read, no second 6.5 GB
+# buffer): tools/fused_backward_ab.py, profiles/r04_fused_backward.md.
+# DTA_CE_FUSED=0 keeps ce_fwd + ce_bwd.
+_CE_FUSED = _os.environ.get("DTA_CE_FUSED", "1") != "0"
+# DTA_CE_FUSED=lds: the variant that holds the row in LDS (ce_fwd_bwd_lds_k),
+# 0.38 ms faster but not bit-identical to ce_fwd + ce_bwd (ce.hip header)
+_CE_FUSED_LDS = _os.environ.get("DTA_CE_FUSED", "1") == "lds"
 _ce_stream: Optional[torch.cuda.Stream] = None
 
 
@@ -739,7 +746,8 @@ def _ce_side_stream() -> torch.cuda.Stream:
 
 class _LMHeadCEFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x2, w, targets, ignore_index, allow_pipe):
+    def forward(ctx, x2, w, targets, ignore_index, allow_pipe,
+                allow_fused=False):
         # NOTE: grad mode is always OFF inside Function.forward — the
         # caller decides pipe eligibility (allow_pipe) where grad state
         # is visible.
@@ -747,6 +755,9 @@ class _LMHeadCEFn(torch.autograd.Function):
         T, _K = x2.shape
         V = w.shape[0]
         pipe = _CE_PIPE and allow_pipe and T >= 2 * _CE_TT
+        # the caller gave the logits up: one kernel reduces each row and
+        # overwrites it with its gradient (ce.hip, ce_fwd_bwd_k)
+        fused = _CE_FUSED and allow_fused and not pipe
         if pipe:
             # tiled: per-(token, vocab) tile CONTIGUOUS buffers — the GEMM
             # writes a tile, the side stream folds its online-softmax
@@ -777,6 +788,18 @@ class _LMHeadCEFn(torch.autograd.Function):
             loss_sum, lse, count = m.ce_finalize(targets, mr, sr, tl,
                                                  ignore_index)
             logits = x2.new_empty(0)
+        elif fused:
+            # the logits buffer comes back holding dlogits for dloss == 1
+            dlog = x2.mm(w.t())
+            # the count depends on the targets alone and the kernel needs
+            # its reciprocal up front: this is the one place it is computed
+            count = (targets != ignore_index).sum()
+            inv = count.clamp(min=1).to(torch.float32).reciprocal()
+            loss_sum, lse, _ = m.ce_fwd_bwd(dlog, targets.contiguous(),
+                                            ignore_index, inv.reshape(1),
+                                            0, _CE_FUSED_LDS)
+            tiles = [dlog]
+            logits = x2.new_empty(0)
         else:
             logits = x2.mm(w.t())
             loss_sum, lse, count = m.ce_fwd(logits, targets, ignore_index)
@@ -785,6 +808,7 @@ class _LMHeadCEFn(torch.autograd.Function):
         ctx.save_for_backward(x2, w, targets, lse, countf, *tiles)
         ctx.ignore_index = ignore_index
         ctx.pipe = pipe
+        ctx.fused = fused
         ctx.dims = (T, V)
         ctx.wgrad = getattr(w, "main_grad", None)
         ctx.mark_non_differentiable(logits)
@@ -799,8 +823,26 @@ class _LMHeadCEFn(torch.autograd.Function):
     def backward(ctx, dloss, _dlogits):
         m = require_ext()
         x2, w, targets, lse, countf, *tiles = ctx.saved_tensors
-        scale_dev = (dloss.to(torch.float32) / countf).reshape(1)
         ii = ctx.ignore_index
+        if ctx.fused:
+            # dlog was made for dloss == 1; the device scalar goes on the
+            # small [T, K] side of each GEMM. PRECISION for dloss != 1:
+            # dloss is rounded to the activation dtype first, so a scale
+            # bf16 cannot hold (1/3, say) puts a relative error of up to
+            # 2^-9 on every head-path gradient, and dx / x2*dl are rounded
+            # once more. The unfused path applies fp32 dloss/count inside
+            # ce_bwd before its single rounding. dloss == 1 (training, the
+            # benchmark) and powers of two (loss scaling) are exact.
+            dlog = tiles[0]
+            dl = dloss.to(x2.dtype)
+            dx = dlog.mm(w) * dl
+            if ctx.wgrad is not None:
+                ctx.wgrad.addmm_(dlog.t(), x2 * dl)
+                dw = None
+            else:
+                dw = dlog.t().mm(x2 * dl)
+            return dx, dw, None, None, None, None
+        scale_dev = (dloss.to(torch.float32) / countf).reshape(1)
         if not ctx.pipe:
             dlog = m.ce_bwd(tiles[0], targets, lse, scale_dev, 0.0, ii,
                             0, True)
@@ -810,7 +852,7 @@ class _LMHeadCEFn(torch.autograd.Function):
                 dw = None
             else:
                 dw = dlog.t().mm(x2)
-            return dx, dw, None, None, None
+            return dx, dw, None, None, None, None
         T, V = ctx.dims
         dx = torch.empty_like(x2)
         dw = None if ctx.wgrad is not None else torch.zeros_like(w)
@@ -833,21 +875,26 @@ class _LMHeadCEFn(torch.autograd.Function):
                     ctx.wgrad[v0:ve].addmm_(dlog.t(), x2[t0:te])
                 else:
                     dw[v0:ve].addmm_(dlog.t(), x2[t0:te])
-        return dx, dw, None, None, None
+        return dx, dw, None, None, None, None
 
 
 def lm_head_ce(x: torch.Tensor, w: torch.Tensor, targets: torch.Tensor,
-               ignore_index: int = -100, need_logits: bool = True):
+               ignore_index: int = -100, need_logits: bool = True,
+               overwrite_logits: bool = False):
     """(loss, logits) = mean-CE(x @ wᵀ, targets) as one node. x [..., E]
     is flattened to [T, E]. With ``need_logits=False`` (training) the
-    pipelined tiled path may engage and logits come back as ``None``."""
+    pipelined tiled path may engage and logits come back as ``None``.
+    ``overwrite_logits=True`` with it gives the logits up for good: one
+    kernel turns the buffer into its own gradient (no second [T, V] pass
+    or buffer) and logits always come back as ``None``."""
     x2 = x.reshape(-1, x.shape[-1])
     if use_hip(x):
         if not x2.is_contiguous():
             x2 = x2.contiguous()
         allow_pipe = not need_logits and torch.is_grad_enabled()
         loss, logits = _LMHeadCEFn.apply(x2, w, targets, ignore_index,
-                                         allow_pipe)
+                                         allow_pipe,
+                                         allow_pipe and overwrite_logits)
         return loss, (logits if logits.numel() else None)
     logits = F.linear(x2, w)
     loss = F.cross_entropy(logits.float(), targets,

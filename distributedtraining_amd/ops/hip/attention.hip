@@ -16,6 +16,10 @@
 //     Row-major panels (pitch D+8) feed A-fragments of the score MFMAs,
 //     transposed [D][LDS_RP] panels feed B-fragments of the accumulating
 //     MFMAs as single 16 B LDS reads.
+//   * seq <= 64 without GQA (the training shape): attn_bwd_fused_k does dq
+//     and dkv in one block from resident 64-row panels, so the operands
+//     leave HBM once; same arithmetic, bit-identical results. Measured
+//     0.249 ms against 0.126 + 0.183 ms (profiles/r04_fused_backward.md).
 //   * Barrier-uniform loops: the trip count depends on blockIdx only, and
 //     a wave with nothing to do in an iteration `continue`s AFTER the
 //     second barrier. Nothing returns or breaks before a __syncthreads.
@@ -552,6 +556,255 @@ __global__ void attn_bwd_dkv_k(const ushort* __restrict__ dout,
   });
 }
 
+// ---------------- backward, whole head in one tile ----------------
+// seq <= 64 and grp == 1 (the miner's training shape): the dq block and the
+// dkv block of a (b, h) load the same four 64-row tiles, so one block does
+// both and Q, K, V, dO and O leave HBM once. Both score walks are kept
+// (S/P/dS recomputed q-major, then k-major), reading the resident panels
+// where the two kernels above read staged tiles and global rows, so every
+// element goes through the same arithmetic in the same order and dq/dk/dv
+// are bit-identical to the two-kernel path. delta and lse live in LDS; the
+// delta global buffer is not needed.
+// LDS: the four operands row-major as two 32-row tiles each, as
+// stage_tile lays them out. The transposed panels are made from those
+// (LDS to LDS) and share one pool with the K/V row-major panels, which the
+// dkv phase reads from registers only:
+//   dq phase:  pool = K rm | V rm | K t      dkv phase: pool = Q t | dO t
+// 47.6 KB at D = 64: three blocks per CU. D = 128 would need 90 KB (one
+// block per CU) and is left on the two-kernel path.
+// No wave returns before the last __syncthreads.
+template <int DTILES>
+DEV bf16x8 load_frag_head(const ushort* rm2, int row, int c0) {
+  return load_frag_rm<DTILES>(rm2 + (row >> 5) * LDS_RM_SIZE<DTILES>,
+                              row & 31, c0);
+}
+
+template <int DTILES>
+__global__ void attn_bwd_fused_k(const ushort* __restrict__ dout,
+                                 const ushort* __restrict__ q,
+                                 const ushort* __restrict__ k,
+                                 const ushort* __restrict__ v,
+                                 const ushort* __restrict__ o,
+                                 const float* __restrict__ lse,
+                                 ushort* __restrict__ dq,
+                                 ushort* __restrict__ dk,
+                                 ushort* __restrict__ dv, AttnGeom geo) {
+  constexpr int RM = LDS_RM_SIZE<DTILES>, TP = LDS_T_SIZE<DTILES>;
+  constexpr int PITCH = LDS_RM_PITCH<DTILES>;
+  static_assert(4 * TP <= 4 * RM + 2 * TP, "Q t | dO t must fit the pool");
+  const AttnCtx c = attn_ctx(geo, q, k, v, dout);
+  const int lane = c.lane, g = c.g, seq = geo.seq, kvl = c.kvl;
+  const int r0 = c.wid * 16;           // this wave's query rows, then key rows
+  const bool live = r0 < seq;
+  const int row = r0 + (lane & 15);    // qrow in the dq phase, krow in dkv
+
+  __shared__ __attribute__((aligned(16))) ushort q_rm[2 * RM];
+  __shared__ __attribute__((aligned(16))) ushort d_rm[2 * RM];
+  __shared__ __attribute__((aligned(16))) ushort pool[4 * RM + 2 * TP];
+  __shared__ float lse_s[64], dlt_s[64];
+  ushort* k_rm = pool;
+  ushort* v_rm = pool + 2 * RM;
+  ushort* k_t = pool + 4 * RM;
+  ushort* q_t = pool;
+  ushort* d_t = pool + 2 * TP;
+
+  // O rows feed delta only: straight to registers, issued before staging
+  const ushort* op = o + c.b * geo.o.batch + c.h * geo.o.head;
+  bf16x8 orow[DTILES / 2];
+#pragma unroll
+  for (int sl = 0; sl < DTILES / 2; ++sl)
+    orow[sl] = load_frag_row(op, geo.o.seq, clamp_row(row, seq),
+                             32 * sl + 8 * g);
+  if (c.tid < 64) lse_s[c.tid] = lse[c.bhid * seq + clamp_row(c.tid, seq)];
+#pragma unroll
+  for (int t2 = 0; t2 < 2; ++t2) {
+    stage_tile<DTILES, false>(q_rm + t2 * RM, c.q, geo.q.seq, 32 * t2, seq,
+                              c.tid);
+    stage_tile<DTILES, false>(d_rm + t2 * RM, c.dout, geo.dout.seq, 32 * t2,
+                              seq, c.tid);
+    stage_tile<DTILES, false>(k_rm + t2 * RM, c.k, geo.k.seq, 32 * t2, seq,
+                              c.tid);
+    stage_tile<DTILES, false>(v_rm + t2 * RM, c.v, geo.v.seq, 32 * t2, seq,
+                              c.tid);
+  }
+  __syncthreads();
+#pragma unroll
+  for (int t2 = 0; t2 < 2; ++t2)
+    stage_tile<DTILES, true>(k_t + t2 * TP, k_rm + t2 * RM, PITCH, 0, 32,
+                             c.tid);
+
+  // ---- dq phase: attn_bwd_dq_k for query rows r0..r0+15 ----
+  {
+    const int qrow = row;
+    bf16x8 qb_[DTILES / 2], dob[DTILES / 2];
+    float dpart = 0.f;
+#pragma unroll
+    for (int sl = 0; sl < DTILES / 2; ++sl) {
+      const int c0 = 32 * sl + 8 * g;
+      qb_[sl] = load_frag_head<DTILES>(q_rm, qrow, c0);
+      dob[sl] = load_frag_head<DTILES>(d_rm, qrow, c0);
+#pragma unroll
+      for (int j = 0; j < 8; ++j)
+        dpart = fmaf(float(dob[sl][j]), float(orow[sl][j]), dpart);
+    }
+    dpart += __shfl_xor(dpart, 16);
+    dpart += __shfl_xor(dpart, 32);
+    const float dlt_q = dpart;
+    if (lane < 16 && qrow < seq) dlt_s[qrow] = dlt_q;
+    const float lse_q = lse_s[qrow] * LOG2E;  // exp2 units
+    __syncthreads();   // K t (and delta, for the dkv phase) visible
+
+    f32x4 acc[DTILES];
+#pragma unroll
+    for (int t = 0; t < DTILES; ++t) acc[t] = f32x4{0, 0, 0, 0};
+    const int blk_kv_end = min(seq, (kvl + 31) & ~31);  // uniform
+    const int my_kv_end = live ? min(seq, r0 + 16) : 0;
+    for (int kv0 = 0; kv0 < blk_kv_end; kv0 += 32) {
+      if (kv0 >= my_kv_end) continue;
+      const ushort* k_rm_t = k_rm + (kv0 >> 5) * RM;
+      const ushort* v_rm_t = v_rm + (kv0 >> 5) * RM;
+      const ushort* k_t_t = k_t + (kv0 >> 5) * TP;
+      f32x4 s0 = {0, 0, 0, 0}, s1 = {0, 0, 0, 0};
+      f32x4 dp0 = {0, 0, 0, 0}, dp1 = {0, 0, 0, 0};
+#pragma unroll
+      for (int sl = 0; sl < DTILES / 2; ++sl) {
+        const int c0 = 32 * sl + 8 * g;
+        bf16x8 ka = load_frag_rm<DTILES>(k_rm_t, lane & 15, c0);
+        bf16x8 kb2 = load_frag_rm<DTILES>(k_rm_t, 16 + (lane & 15), c0);
+        bf16x8 va = load_frag_rm<DTILES>(v_rm_t, lane & 15, c0);
+        bf16x8 vb2 = load_frag_rm<DTILES>(v_rm_t, 16 + (lane & 15), c0);
+        s0 = mfma_bf16(ka, qb_[sl], s0);
+        s1 = mfma_bf16(kb2, qb_[sl], s1);
+        dp0 = mfma_bf16(va, dob[sl], dp0);
+        dp1 = mfma_bf16(vb2, dob[sl], dp1);
+      }
+      if (c.thr) {
+        const DropHashes dh = attn_drop_hashes(c, qrow, kv0);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          dp0[r] = attn_drop_keep(dp0[r], dh.h0, r, geo.drop);
+          dp1[r] = attn_drop_keep(dp1[r], dh.h1, r, geo.drop);
+        }
+      }
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int k0a = kv0 + 4 * g + r, k1a = k0a + 16;
+        const float P0 = attn_visible(qrow, k0a, kvl)
+                             ? __builtin_exp2f(s0[r] * c.sc2 - lse_q) : 0.f;
+        const float P1 = attn_visible(qrow, k1a, kvl)
+                             ? __builtin_exp2f(s1[r] * c.sc2 - lse_q) : 0.f;
+        s0[r] = P0 * (dp0[r] - dlt_q);
+        s1[r] = P1 * (dp1[r] - dlt_q);
+      }
+      bf16x8 dsa = scores_to_afrag(s0, s1, lane);
+#pragma unroll
+      for (int t = 0; t < DTILES; ++t) {
+        bf16x8 kcb = load_frag_col_lds(k_t_t, 8 * g, 16 * t + (lane & 15));
+        acc[t] = mfma_bf16(dsa, kcb, acc[t]);
+      }
+    }
+    if (live)
+      store_acc_tile<DTILES>(dq + c.b * geo.dq.batch + c.h * geo.dq.head,
+                             geo.dq.seq, r0, seq, lane, acc,
+                             f32x4{geo.scale, geo.scale, geo.scale,
+                                   geo.scale});
+  }
+
+  // ---- dkv phase: attn_bwd_dkv_k<.., false> for key rows r0..r0+15 ----
+  const int krow = row;
+  bf16x8 kb_[DTILES / 2], vbf[DTILES / 2];
+#pragma unroll
+  for (int sl = 0; sl < DTILES / 2; ++sl) {
+    kb_[sl] = load_frag_head<DTILES>(k_rm, krow, 32 * sl + 8 * g);
+    vbf[sl] = load_frag_head<DTILES>(v_rm, krow, 32 * sl + 8 * g);
+  }
+  __syncthreads();   // every wave is done with K rm | V rm | K t
+#pragma unroll
+  for (int t2 = 0; t2 < 2; ++t2) {
+    stage_tile<DTILES, true>(q_t + t2 * TP, q_rm + t2 * RM, PITCH, 0, 32,
+                             c.tid);
+    stage_tile<DTILES, true>(d_t + t2 * TP, d_rm + t2 * RM, PITCH, 0, 32,
+                             c.tid);
+  }
+  __syncthreads();
+
+  f32x4 acck[DTILES], accv[DTILES];
+#pragma unroll
+  for (int t = 0; t < DTILES; ++t) {
+    acck[t] = f32x4{0, 0, 0, 0};
+    accv[t] = f32x4{0, 0, 0, 0};
+  }
+  // all 64 key rows padding: zero dk/dv, skip the walk (uniform)
+  const int q_start = (0 >= kvl) ? seq : 0;
+  for (int q0 = q_start; q0 < seq; q0 += 32) {
+    if (!live || q0 + 31 < r0) continue;   // fully below the diagonal
+    const ushort* q_rm_t = q_rm + (q0 >> 5) * RM;
+    const ushort* d_rm_t = d_rm + (q0 >> 5) * RM;
+    f32x4 s0 = {0, 0, 0, 0}, s1 = {0, 0, 0, 0};
+    f32x4 dp0 = {0, 0, 0, 0}, dp1 = {0, 0, 0, 0};
+#pragma unroll
+    for (int sl = 0; sl < DTILES / 2; ++sl) {
+      const int c0 = 32 * sl + 8 * g;
+      bf16x8 qa = load_frag_rm<DTILES>(q_rm_t, lane & 15, c0);
+      bf16x8 qa1 = load_frag_rm<DTILES>(q_rm_t, 16 + (lane & 15), c0);
+      s0 = mfma_bf16(qa, kb_[sl], s0);
+      s1 = mfma_bf16(qa1, kb_[sl], s1);
+      bf16x8 doa = load_frag_rm<DTILES>(d_rm_t, lane & 15, c0);
+      bf16x8 doa1 = load_frag_rm<DTILES>(d_rm_t, 16 + (lane & 15), c0);
+      dp0 = mfma_bf16(doa, vbf[sl], dp0);
+      dp1 = mfma_bf16(doa1, vbf[sl], dp1);
+    }
+    f32x4 p0, p1, ds0, ds1;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int qa0 = q0 + 4 * g + r, qa1 = qa0 + 16;
+      const bool v0 = qa0 < seq && attn_visible(qa0, krow, kvl);
+      const bool v1 = qa1 < seq && attn_visible(qa1, krow, kvl);
+      const float l0 = lse_s[v0 ? qa0 : 0] * LOG2E;
+      const float l1 = lse_s[v1 ? qa1 : 0] * LOG2E;
+      p0[r] = v0 ? __builtin_exp2f(s0[r] * c.sc2 - l0) : 0.f;
+      p1[r] = v1 ? __builtin_exp2f(s1[r] * c.sc2 - l1) : 0.f;
+      const float d0 = dlt_s[(qa0 < seq) ? qa0 : 0];
+      const float d1 = dlt_s[(qa1 < seq) ? qa1 : 0];
+      if (c.thr) {
+        const uint64_t hk0 =
+            rng_attn_hash(c.drop_s2, uint32_t(qa0), uint32_t(krow) >> 2);
+        const uint64_t hk1 =
+            rng_attn_hash(c.drop_s2, uint32_t(qa1), uint32_t(krow) >> 2);
+        const float m0 =
+            rng_keep(hk0, krow & 3, c.thr) ? geo.drop.inv_keep : 0.f;
+        const float m1 =
+            rng_keep(hk1, krow & 3, c.thr) ? geo.drop.inv_keep : 0.f;
+        ds0[r] = p0[r] * (m0 * dp0[r] - d0);
+        ds1[r] = p1[r] * (m1 * dp1[r] - d1);
+        p0[r] *= m0;
+        p1[r] *= m1;
+      } else {
+        ds0[r] = p0[r] * (dp0[r] - d0);
+        ds1[r] = p1[r] * (dp1[r] - d1);
+      }
+    }
+    bf16x8 pa = scores_to_afrag(p0, p1, lane);
+    bf16x8 dsa = scores_to_afrag(ds0, ds1, lane);
+    const ushort* d_t_t = d_t + (q0 >> 5) * TP;
+    const ushort* q_t_t = q_t + (q0 >> 5) * TP;
+#pragma unroll
+    for (int t = 0; t < DTILES; ++t) {
+      bf16x8 dob2 = load_frag_col_lds(d_t_t, 8 * g, 16 * t + (lane & 15));
+      accv[t] = mfma_bf16(pa, dob2, accv[t]);
+      bf16x8 qcb = load_frag_col_lds(q_t_t, 8 * g, 16 * t + (lane & 15));
+      acck[t] = mfma_bf16(dsa, qcb, acck[t]);
+    }
+  }
+  if (!live) return;
+  ushort* dkp = dk + c.b * geo.dkv.batch + c.h * geo.dkv.head;
+  ushort* dvp = dv + c.b * geo.dkv.batch + c.h * geo.dkv.head;
+  for_acc_rows<DTILES>(r0, seq, lane, [&](int t, int r, int rw, int col) {
+    dkp[int64_t(rw) * geo.dkv.seq + col] = f2bf(acck[t][r] * geo.scale);
+    dvp[int64_t(rw) * geo.dkv.seq + col] = f2bf(accv[t][r]);
+  });
+}
+
 // ---------------- decode (KV-cache serving path) ----------------
 // One new query per (b,h) against a cached K/V of length kvlen (no mask:
 // every cached key is attended). ONE BLOCK per (b,h): the 4 waves split
@@ -782,6 +1035,20 @@ void launch_attn_bwd_dkv(const bf16_t* dout, const bf16_t* q,
     kern<<<attn_grid(geo), 256, 0, s>>>(dout, q, k, v, lse, delta, dk32,
                                         dv32, dk, dv, geo);
   });
+}
+
+void launch_attn_bwd_fused(const bf16_t* dout, const bf16_t* q,
+                           const bf16_t* k, const bf16_t* v, const bf16_t* o,
+                           const float* lse, bf16_t* dq, bf16_t* dk,
+                           bf16_t* dv, const AttnGeom& geo, hipStream_t s) {
+  // dta_attn_bwd_fused_shape(geo) holds: one 64-row tile, hd 32 or 64
+  const dim3 grid(1, int64_t(geo.B) * geo.H);
+  if (geo.hd == 64)
+    attn_bwd_fused_k<4><<<grid, 256, 0, s>>>(dout, q, k, v, o, lse, dq, dk,
+                                             dv, geo);
+  else
+    attn_bwd_fused_k<2><<<grid, 256, 0, s>>>(dout, q, k, v, o, lse, dq, dk,
+                                             dv, geo);
 }
 
 void launch_mfma_probe_16(const bf16_t* A, const bf16_t* B, float* D,

@@ -4,6 +4,7 @@
 #include <ATen/hip/HIPContext.h>
 
 #include <algorithm>
+#include <atomic>
 #include <vector>
 
 #include "dta_kernels.h"
@@ -439,6 +440,54 @@ Tensor ce_bwd(Tensor logits, Tensor targets, Tensor lse, Tensor scale_dev,
   return dl;
 }
 
+// Training CE in one kernel: logits [rows, vocab] is OVERWRITTEN with
+// dlogits = inv_count * (softmax - onehot), zeros on ignored rows.
+// inv_count_dev: fp32 device scalar 1/max(count, 1), computed from targets
+// before the call (no host sync). max_rows: rows in flight, 0 = automatic.
+// lds_row: the variant that holds the row in LDS (lse then agrees with
+// ce_fwd to rounding only); rows too wide for LDS take the default variant.
+// Returns [loss_sum, lse, count] as ce_fwd does.
+std::vector<Tensor> ce_fwd_bwd(Tensor logits, Tensor targets,
+                               int64_t ignore_index, Tensor inv_count_dev,
+                               int64_t max_rows, bool lds_row) {
+  check_bf16(logits, "logits");
+  TORCH_CHECK(logits.dim() == 2 && logits.is_contiguous(),
+              "logits must be a contiguous [rows, vocab] tensor");
+  TORCH_CHECK(targets.is_cuda() && targets.scalar_type() == torch::kInt64 &&
+                  targets.is_contiguous() &&
+                  targets.numel() == logits.size(0),
+              "targets must be a contiguous int64 [rows] GPU tensor");
+  check_f32(inv_count_dev, "inv_count");
+  TORCH_CHECK(inv_count_dev.numel() == 1, "inv_count must be one element");
+  TORCH_CHECK(max_rows >= 0, "max_rows must be >= 0");
+  const int64_t rows = logits.size(0), vocab = logits.size(1);
+  auto lse = torch::empty({rows}, logits.options().dtype(torch::kFloat32));
+  auto loss = torch::zeros({1}, logits.options().dtype(torch::kFloat32));
+  auto count = torch::zeros({1}, logits.options().dtype(torch::kInt32));
+  const auto* prop = at::cuda::getCurrentDeviceProperties();
+  if (lds_row &&
+      launch_ce_fwd_bwd_lds(bfp_mut(logits), targets.data_ptr<int64_t>(),
+                            rows, vocab, ignore_index,
+                            inv_count_dev.data_ptr<float>(),
+                            lse.data_ptr<float>(), loss.data_ptr<float>(),
+                            count.data_ptr<int>(), prop->multiProcessorCount,
+                            int64_t(prop->maxSharedMemoryPerMultiProcessor),
+                            stream())) {
+    const hipError_t err = hipGetLastError();
+    TORCH_CHECK(err == hipSuccess, "ce_fwd_bwd (LDS row) launch failed: ",
+                hipGetErrorString(err));
+    return {loss.squeeze(0), lse, count.squeeze(0)};
+  }
+  const int blocks =
+      max_rows ? int(std::min<int64_t>(max_rows, 65535))
+               : dta_ce_fwd_bwd_blocks(vocab, prop->multiProcessorCount);
+  launch_ce_fwd_bwd(bfp_mut(logits), targets.data_ptr<int64_t>(), rows, vocab,
+                    ignore_index, inv_count_dev.data_ptr<float>(),
+                    lse.data_ptr<float>(), loss.data_ptr<float>(),
+                    count.data_ptr<int>(), blocks, stream());
+  return {loss.squeeze(0), lse, count.squeeze(0)};
+}
+
 // ---- embedding -------------------------------------------------------------
 // pos: optional int32 [1] device offset for the wpe row (graph decode)
 Tensor embedding_fwd(Tensor ids, Tensor wte, Tensor wpe, Tensor pos) {
@@ -624,7 +673,25 @@ std::vector<Tensor> attn_fwd(Tensor q, Tensor k, Tensor v, double scale,
   return {o, lse};  // caller views o as [B,H,S,D] via permute(0,2,1,3)
 }
 
-// The backward both entry points share: delta alloc -> dQ -> dK/dV.
+// Single-tile fused backward: on unless DTA_ATTN_BWD_FUSED=0, or
+// attn_bwd_fused_enable() said otherwise (tests and the A/B tool run both
+// paths in one process). The counter tells a caller which path a call took.
+// Atomics: autograd runs the backward on its own threads.
+static std::atomic<int> g_attn_bwd_fused_force{-1};   // -1: environment
+static std::atomic<int64_t> g_attn_bwd_fused_calls{0};
+static bool attn_bwd_fused_on() {
+  const int force = g_attn_bwd_fused_force.load();
+  return force < 0 ? dta_attn_bwd_fused_default() : force != 0;
+}
+bool attn_bwd_fused_enable(bool on) {
+  const bool was = attn_bwd_fused_on();
+  g_attn_bwd_fused_force.store(on ? 1 : 0);
+  return was;
+}
+int64_t attn_bwd_fused_calls() { return g_attn_bwd_fused_calls.load(); }
+
+// The backward both entry points share: one fused launch for a single-tile
+// head, else delta alloc -> dQ -> dK/dV.
 // dq_v: [B,S,H,D] destination view (contiguous D), always written.
 // grp == 1: dk/dv are stored straight into the [B,S,Hk,D] views dk_v/dv_v.
 // GQA: the q heads fold into zeroed fp32 [B,Hk,S,D] buffers with atomics;
@@ -641,6 +708,16 @@ static std::pair<Tensor, Tensor> attn_bwd_into(
   AttnGeom geo = make_geom(q, k, v, o_bshd, dout, scale);
   geo.dq = strides_bshd(dq_v);
   set_mask_drop(geo, kvlen, rng, site, p, B);
+  if (attn_bwd_fused_on() && dta_attn_bwd_fused_shape(geo)) {
+    TORCH_CHECK(dk_v.stride(3) == 1 && dk_v.strides() == dv_v.strides(),
+                "dk/dv views need contiguous head_dim and equal strides");
+    geo.dkv = strides_bshd(dk_v);
+    launch_attn_bwd_fused(bfp(dout), bfp(q), bfp(k), bfp(v), bfp(o_bshd),
+                          lse.data_ptr<float>(), bfp_mut(dq_v), bfp_mut(dk_v),
+                          bfp_mut(dv_v), geo, stream());
+    ++g_attn_bwd_fused_calls;
+    return {Tensor(), Tensor()};
+  }
   auto delta = torch::empty({B * H, S}, lse.options());
   launch_attn_bwd_dq(bfp(dout), bfp(q), bfp(k), bfp(v), bfp(o_bshd),
                      lse.data_ptr<float>(), delta.data_ptr<float>(),
@@ -765,6 +842,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("grad_merge_weights", &grad_merge_weights);
   m.def("ce_fwd", &ce_fwd);
   m.def("ce_bwd", &ce_bwd);
+  m.def("ce_fwd_bwd", &ce_fwd_bwd, pybind11::arg("logits"),
+        pybind11::arg("targets"), pybind11::arg("ignore_index"),
+        pybind11::arg("inv_count_dev"), pybind11::arg("max_rows") = 0,
+        pybind11::arg("lds_row") = false);
   m.def("ce_chunk", &ce_chunk);
   m.def("ce_finalize", &ce_finalize);
   m.def("head_loss_fwd", &head_loss_fwd);
@@ -778,6 +859,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_fwd", &attn_fwd);
   m.def("attn_bwd", &attn_bwd);
   m.def("attn_bwd_packed", &attn_bwd_packed);
+  m.def("attn_bwd_fused_enable", &attn_bwd_fused_enable);
+  m.def("attn_bwd_fused_calls", &attn_bwd_fused_calls);
   m.def("attn_decode", &attn_decode);
   m.def("mfma_selftest_16", &mfma_selftest_16);
   m.def("mfma_selftest_32", &mfma_selftest_32);

@@ -177,6 +177,29 @@ void launch_ce_bwd(const bf16_t* logits, const int64_t* targets,
                    int64_t ignore_index, int64_t v0, bool nt,
                    bf16_t* dlogits, int64_t rows, int64_t vocab,
                    hipStream_t s);
+// Training: ce_fwd, then ce_bwd with scale *inv_count, row by row in one
+// kernel, IN PLACE (logits becomes dlogits). A block's second sweep reads
+// its row back from cache, so at most max_blocks rows are in flight.
+void launch_ce_fwd_bwd(bf16_t* logits, const int64_t* targets, int64_t rows,
+                       int64_t vocab, int64_t ignore_index,
+                       const float* inv_count, float* lse, float* loss_sum,
+                       int* count, int max_blocks, hipStream_t s);
+// The same with the row held in LDS between the sweeps, one block per CU.
+// False, and nothing launched, when a row (2 * vocab bytes) does not fit
+// lds_limit, the LDS a block may have: the caller takes the variant above.
+bool launch_ce_fwd_bwd_lds(bf16_t* logits, const int64_t* targets,
+                           int64_t rows, int64_t vocab, int64_t ignore_index,
+                           const float* inv_count, float* lse,
+                           float* loss_sum, int* count, int n_cu,
+                           int64_t lds_limit, hipStream_t s);
+// Rows ce_fwd_bwd keeps in flight: half the 256 MiB Infinity Cache's worth,
+// at least one per CU (wider rows then spill to HBM, still correct) and at
+// most the 4096 blocks the other CE kernels launch.
+inline int dta_ce_fwd_bwd_blocks(int64_t vocab, int n_cu) {
+  const int64_t fit = (int64_t(128) << 20) / (2 * (vocab > 0 ? vocab : 1));
+  const int64_t lo = n_cu > 0 ? n_cu : 1;
+  return int(fit < lo ? lo : (fit > 4096 ? 4096 : fit));
+}
 // pipelined head-GEMM+CE: per-tile online-softmax update + finalize
 void launch_ce_chunk(const bf16_t* chunk, int64_t ld, int64_t rows,
                      int64_t cols, const int64_t* targets, int64_t v0,
@@ -270,6 +293,26 @@ void launch_attn_bwd_dkv(const bf16_t* dout, const bf16_t* q,
                          const float* delta, float* dk32, float* dv32,
                          bf16_t* dk, bf16_t* dv, const AttnGeom& geo,
                          hipStream_t s);
+// Shapes the single-tile fused backward takes: the whole head is one
+// 64-row tile, no GQA fold, and a head dim whose panels fit LDS (128 does
+// not: 90 KB). Everything else runs dq then dkv.
+inline bool dta_attn_bwd_fused_shape(const AttnGeom& geo) {
+  return geo.seq <= 64 && geo.grp == 1 && (geo.hd == 32 || geo.hd == 64);
+}
+// DTA_ATTN_BWD_FUSED=0 keeps eligible shapes on the two-kernel path too.
+inline bool dta_attn_bwd_fused_default() {
+  static const bool en = [] {
+    const char* e = ::getenv("DTA_ATTN_BWD_FUSED");
+    return !(e && e[0] == '0');
+  }();
+  return en;
+}
+// dq + dk/dv of one (b, h) in one block; needs dta_attn_bwd_fused_shape.
+// delta stays in LDS. dk/dv are stored with the dkv strides.
+void launch_attn_bwd_fused(const bf16_t* dout, const bf16_t* q,
+                           const bf16_t* k, const bf16_t* v, const bf16_t* o,
+                           const float* lse, bf16_t* dq, bf16_t* dk,
+                           bf16_t* dv, const AttnGeom& geo, hipStream_t s);
 
 // len_p: device cache-length counter (effective kvlen = *len_p + 1) for
 // hipGraph-replayable decode; null = host kvlen scalar
