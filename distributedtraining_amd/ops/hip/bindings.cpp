@@ -250,15 +250,15 @@ void adamw_step(Tensor master, Tensor grad, Tensor m, Tensor v,
   const float* bcp = bc.numel() ? bc.data_ptr<float>() : nullptr;
   launch_adamw(master.data_ptr<float>(), grad.data_ptr(), gb,
                m.data_ptr<float>(), v.data_ptr<float>(), outp, int(step),
-               bcp, float(lr), float(beta1), float(beta2), float(eps),
-               float(wd), master.numel(), stream());
+               bcp, float(lr), beta1, beta2, float(eps), float(wd),
+               master.numel(), stream());
 }
 
 void adamw_tick(Tensor t, Tensor bc, double beta1, double beta2) {
   TORCH_CHECK(t.scalar_type() == torch::kInt32 && t.is_cuda(), "t int32 gpu");
   check_f32(bc, "bc");
-  launch_adamw_tick(t.data_ptr<int>(), bc.data_ptr<float>(), float(beta1),
-                    float(beta2), stream());
+  launch_adamw_tick(t.data_ptr<int>(), bc.data_ptr<float>(), beta1, beta2,
+                    stream());
 }
 
 // column sum of a [rows, cols] bf16 matrix -> fp32 [cols] (bias gradient)

@@ -54,11 +54,14 @@ void launch_axpy(float* w, const float* x, float alpha, int64_t n,
                  hipStream_t s);
 void launch_nan_any(const float* x, int64_t n, int* flag, hipStream_t s);
 void launch_l2norm_sq(const float* x, int64_t n, float* out, hipStream_t s);
+// beta1/beta2 stay double up to here: 1 - beta and the bias corrections
+// 1 - beta^t are formed in double and rounded once (in fp32, 1 - 0.999f is
+// 1.3e-5 off 0.001, and v with it)
 void launch_adamw(float* master, const void* grad, bool grad_is_bf16,
                   float* m, float* v, bf16_t* out_bf16, int step,
-                  const float* bc_p, float lr, float beta1, float beta2,
+                  const float* bc_p, float lr, double beta1, double beta2,
                   float eps, float wd, int64_t n, hipStream_t s);
-void launch_adamw_tick(int* t, float* bc, float beta1, float beta2,
+void launch_adamw_tick(int* t, float* bc, double beta1, double beta2,
                        hipStream_t s);
 void launch_colsum(const bf16_t* x, float* part, float* out, int64_t rows,
                    int cols, int stripes, hipStream_t s);

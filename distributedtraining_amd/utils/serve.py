@@ -23,6 +23,17 @@ from ..models import generate
 log = logging.getLogger(__name__)
 
 
+def _cached_decode(model, device) -> bool:
+    """KV-cache decode where the model has one and, on the GPU, a head dim
+    the decode kernel is instantiated for (64 / 128, hip/attention.hip);
+    other models re-forward the context through the training kernels."""
+    if not hasattr(model, "prefill"):
+        return False
+    cfg = model.cfg
+    return (torch.device(device).type != "cuda"
+            or cfg.n_embd // cfg.n_head in (64, 128))
+
+
 class InferenceServer:
     def __init__(self, model, device, host: str = "127.0.0.1",
                  port: int = 0, max_new_tokens_cap: int = 256):
@@ -89,7 +100,8 @@ class InferenceServer:
             out = generate(self.model, ids, mnt, temperature=temperature,
                            top_k=top_k, top_p=top_p,
                            eos_token_id=None if eos is None else int(eos),
-                           use_cache=hasattr(self.model, "prefill"))
+                           use_cache=_cached_decode(self.model,
+                                                    self.device))
         self.served += 1
         return {"ids": out.tolist()}
 
