@@ -155,11 +155,19 @@ class CommConfig:
     device: str = "cpu"
     # wire dtype for the gather-based exchanges (score_weighted /
     # parameterized strategies need all deltas resident): "fp32" is exact;
-    # "bf16" halves xGMI bytes + gather footprint (needed for Llama-scale
-    # models at 8 ranks); "int8" quarters them via blockwise-absmax
+    # "bf16" halves the xGMI bytes; "int8" quarters them via blockwise-absmax
     # quantization (worst-case element error absmax(4096-block)/127).
-    # mean/nesterov all-reduce stays fp32 always.
+    # mean/nesterov all-reduce stays fp32 always. The wire dtype alone does
+    # NOT shrink the resident gather: see resident_dtype.
     exchange_dtype: str = "fp32"
+    # what the gathered deltas look like in HBM. "fp32": the gather is
+    # expanded to [world, P] fp32 (world x P x 4 bytes at any wire dtype).
+    # "wire": it stays in exchange_dtype form (PackedDeltas) and the merge /
+    # grad_W / axpy kernels dequantise in registers — the setting Llama-scale
+    # gathers at 8 ranks need (8 Llama-3-8B deltas: 64 GB int8, 128 GB bf16,
+    # 256 GB fp32). Applies to score_weighted / parameterized / genetic
+    # merges and to validation_round.
+    resident_dtype: str = "fp32"
 
 
 @dataclass

@@ -38,6 +38,7 @@ __all__ = [
     "decode_attention", "rope", "adamw_step", "delta_sub", "axpy_",
     "weighted_merge",
     "grad_merge_weights", "has_nan", "l2norm",
+    "quantize_blockwise_int8", "dequantize_blockwise_int8",
     "dropout", "rng_tick",
 ]
 
@@ -1108,15 +1109,70 @@ def delta_sub(w: torch.Tensor, base: torch.Tensor,
     return out
 
 
-def axpy_(w: torch.Tensor, x: torch.Tensor, alpha: float = 1.0) -> torch.Tensor:
-    """w += alpha·x (reference delta apply: validation_logic.py:252-259)."""
+def _packed(x) -> bool:
+    """A parallel.comm.PackedDeltas (named by shape: comm imports ops)."""
+    return not isinstance(x, torch.Tensor) and hasattr(x, "kind")
+
+
+def _packed_args(pd):
+    """(data, scales, block) as the packed bindings take them."""
+    scales = (pd.scales if pd.scales is not None
+              else torch.empty(0, dtype=torch.float32, device=pd.data.device))
+    return pd.data, scales, pd.block
+
+
+def quantize_blockwise_int8(flat: torch.Tensor, block: int = 4096,
+                            base: Optional[torch.Tensor] = None):
+    """(int8 codes [nb*block], fp32 scales [nb]) of ``flat``, or of
+    ``flat - base``. The definition is parallel.comm.quantize_blockwise_int8
+    (the CPU path); the GPU kernel equals it bit for bit, reads both planes
+    once and never writes the fp32 difference."""
+    if use_hip(flat):
+        def plane(t):
+            # the kernel reads 16 B vectors: a row of an odd-width stack
+            # is copied to an allocation of its own
+            t = t.contiguous()
+            return t if t.data_ptr() % 16 == 0 else t.clone()
+        q, scale = require_ext().quantize_int8(
+            plane(flat), flat.new_empty(0) if base is None else plane(base),
+            block)
+        return q, scale
+    from ..parallel.comm import quantize_blockwise_int8 as _q
+    return _q(flat if base is None else flat.float() - base.float(), block)
+
+
+def dequantize_blockwise_int8(q: torch.Tensor, scale: torch.Tensor,
+                              numel: int, block: int = 4096) -> torch.Tensor:
+    """fp32 [numel] of one quantised row: float(q) * scale per block."""
+    if use_hip(q):
+        out = torch.zeros(numel, dtype=torch.float32, device=q.device)
+        # 1.0 * d + 0.0 is d
+        require_ext().axpy_packed(out, q.view(1, -1), scale.view(1, -1),
+                                  block, 0, 1.0)
+        return out
+    from ..parallel.comm import dequantize_blockwise_int8 as _dq
+    return _dq(q, scale, numel, block)
+
+
+def axpy_(w: torch.Tensor, x, alpha: float = 1.0) -> torch.Tensor:
+    """w += alpha·x (reference delta apply: validation_logic.py:252-259).
+    ``x``: a tensor, or ``(PackedDeltas, i)`` for row ``i`` of a packed
+    gather — dequantised in registers, no fp32 copy of the delta."""
+    if isinstance(x, tuple):
+        pd, i = x
+        if pd.kind == "fp32":
+            return axpy_(w, pd.data[i], alpha)
+        if use_hip(w):
+            require_ext().axpy_packed(w, *_packed_args(pd), i, alpha)
+            return w
+        return w.add_(pd.row(i).to(w.dtype), alpha=alpha)
     if use_hip(w):
         require_ext().axpy(w, x, alpha)
         return w
     return w.add_(x.to(w.dtype), alpha=alpha)
 
 
-def weighted_merge(base: torch.Tensor, deltas: torch.Tensor,
+def weighted_merge(base: torch.Tensor, deltas,
                    W: torch.Tensor, offsets: torch.Tensor,
                    out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """merged[e] = Σ_i W[i, seg(e)] · (base[e] + deltas[i,e]).
@@ -1124,30 +1180,45 @@ def weighted_merge(base: torch.Tensor, deltas: torch.Tensor,
     ``W`` is [N, S] per-(miner, parameter-tensor) merge weights; ``offsets``
     [S+1] the flat-buffer segment boundaries. Reference semantics:
     averaging_logic.py:422-470 (get_averaged_params over per-param weights).
+    ``deltas``: [N, P] fp32, or a PackedDeltas (bf16 / int8 stay compressed
+    in memory; the result equals this call on ``deltas.dequantize()``).
     """
+    if _packed(deltas) and deltas.kind == "fp32":
+        deltas = deltas.data
     N, P = deltas.shape
     if out is None:
         out = torch.empty_like(base)
     if use_hip(base):
+        if _packed(deltas):
+            require_ext().weighted_merge_packed(
+                base, *_packed_args(deltas), W, offsets.to(base.device), out)
+            return out
         require_ext().weighted_merge(base, deltas, W, offsets.to(base.device), out)
         return out
     seg = _seg_ids(offsets, P)
     acc = torch.zeros(P, dtype=torch.float32)
     for i in range(N):
-        acc += W[i].float()[seg] * (base.float() + deltas[i].float())
+        di = deltas.row(i) if _packed(deltas) else deltas[i].float()
+        acc += W[i].float()[seg] * (base.float() + di)
     out.copy_(acc.to(out.dtype))
     return out
 
 
 def grad_merge_weights(g: torch.Tensor, base: torch.Tensor,
-                       deltas: torch.Tensor, merged: torch.Tensor,
+                       deltas, merged: torch.Tensor,
                        offsets: torch.Tensor) -> torch.Tensor:
     """grad_W[i,j] = Σ_{e∈seg j} g[e] · (base[e]+deltas[i,e] − merged[e]).
 
-    The averager's manual meta-gradient (averaging_logic.py:512-522)."""
+    The averager's manual meta-gradient (averaging_logic.py:512-522).
+    ``deltas``: [N, P] fp32 or a PackedDeltas, as in weighted_merge."""
+    if _packed(deltas) and deltas.kind == "fp32":
+        deltas = deltas.data
     N, P = deltas.shape
     S = offsets.numel() - 1
     if use_hip(g):
+        if _packed(deltas):
+            return require_ext().grad_merge_weights_packed(
+                g, base, *_packed_args(deltas), merged, offsets.to(g.device))
         return require_ext().grad_merge_weights(g, base, deltas, merged,
                                                 offsets.to(g.device))
     seg = _seg_ids(offsets, P)
@@ -1155,7 +1226,8 @@ def grad_merge_weights(g: torch.Tensor, base: torch.Tensor,
     diff_base = base.float() - merged.float()
     gf = g.float()
     for i in range(N):
-        contrib = gf * (diff_base + deltas[i].float())
+        di = deltas.row(i) if _packed(deltas) else deltas[i].float()
+        contrib = gf * (diff_base + di)
         gw[i] = torch.zeros(S).index_add_(0, seg, contrib)
     return gw
 

@@ -291,13 +291,10 @@ void weighted_merge(Tensor base, Tensor deltas, Tensor W, Tensor offsets,
                         out.data_ptr<float>(), stream());
 }
 
-Tensor grad_merge_weights(Tensor g, Tensor base, Tensor deltas, Tensor merged,
-                          Tensor offsets) {
-  check_f32(base, "base"); check_f32(deltas, "deltas");
-  const int n_models = int(deltas.size(0));
-  const int n_segs = int(offsets.numel() - 1);
-  const int64_t P = base.numel();
-  // build boundary-aligned chunks host-side (<=1M elements each)
+// boundary-aligned chunk table for grad_W: [n_chunks, 3] int64 rows
+// (start, end, seg) on base's device, none crossing a segment, <= 1M
+// elements each
+Tensor grad_w_chunks(const Tensor& offsets, const Tensor& base, int n_segs) {
   auto offs_cpu = offsets.to(torch::kCPU).contiguous();
   const int64_t* op = offs_cpu.data_ptr<int64_t>();
   std::vector<int64_t> chunks;
@@ -308,10 +305,20 @@ Tensor grad_merge_weights(Tensor g, Tensor base, Tensor deltas, Tensor merged,
       chunks.push_back(std::min(s0 + CH, op[j + 1]));
       chunks.push_back(j);
     }
-  const int n_chunks = int(chunks.size() / 3);
-  auto ch = torch::from_blob(chunks.data(), {int64_t(chunks.size())},
-                             torch::kInt64)
-                .to(base.device());
+  // a blocking copy: the vector may die with this frame
+  return torch::from_blob(chunks.data(), {int64_t(chunks.size())},
+                          torch::kInt64)
+      .to(base.device());
+}
+
+Tensor grad_merge_weights(Tensor g, Tensor base, Tensor deltas, Tensor merged,
+                          Tensor offsets) {
+  check_f32(base, "base"); check_f32(deltas, "deltas");
+  const int n_models = int(deltas.size(0));
+  const int n_segs = int(offsets.numel() - 1);
+  const int64_t P = base.numel();
+  auto ch = grad_w_chunks(offsets, base, n_segs);
+  const int n_chunks = int(ch.numel() / 3);
   auto gw = torch::zeros({n_models, n_segs},
                          base.options().dtype(torch::kFloat32));
   const bool gb = g.scalar_type() == torch::kBFloat16;
@@ -321,6 +328,131 @@ Tensor grad_merge_weights(Tensor g, Tensor base, Tensor deltas, Tensor merged,
                             ch.data_ptr<int64_t>(), n_models, n_chunks, P,
                             gw.data_ptr<float>(), n_segs, stream());
   return gw;
+}
+
+// ---- packed deltas (bf16, or int8 codes + scales) ---------------------------
+bool aligned16(const Tensor& t) {
+  return reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0;
+}
+
+// data [N, P] bf16 with scales empty, or data [N, nb*block] int8 with scales
+// [N, nb] fp32; P is the length of a dequantised row.
+PackedView packed_view(const Tensor& data, const Tensor& scales, int64_t P,
+                       int64_t block) {
+  TORCH_CHECK(data.is_cuda() && data.dim() == 2 && data.is_contiguous(),
+              "packed data must be a contiguous [N, cols] GPU tensor");
+  TORCH_CHECK(data.size(0) >= 1 && data.size(0) <= DTA_MERGE_MAX_MODELS,
+              "packed deltas: 1 <= n_models <= ", DTA_MERGE_MAX_MODELS);
+  TORCH_CHECK(aligned16(data), "packed data must be 16-byte aligned");
+  TORCH_CHECK(P >= 1, "packed deltas: empty plane");
+  if (data.scalar_type() == torch::kBFloat16) {
+    TORCH_CHECK(data.size(1) == P, "bf16 deltas must be [N, P]");
+    return PackedView{data.data_ptr(), nullptr, P, 0, 0, DELTA_BF16};
+  }
+  TORCH_CHECK(data.scalar_type() == torch::kInt8,
+              "packed data must be bf16 or int8");
+  TORCH_CHECK(block >= DTA_QUANT_MIN_BLOCK && block <= DTA_QUANT_MAX_BLOCK &&
+                  (block & (block - 1)) == 0,
+              "block must be a power of two in [", DTA_QUANT_MIN_BLOCK, ", ",
+              DTA_QUANT_MAX_BLOCK, "]");
+  const int64_t nb = (P + block - 1) / block;
+  TORCH_CHECK(data.size(1) == nb * block,
+              "int8 codes must be [N, nb*block], nb = ceil(P / block)");
+  check_f32(scales, "scales");
+  TORCH_CHECK(scales.dim() == 2 && scales.size(0) == data.size(0) &&
+                  scales.size(1) == nb, "scales must be [N, nb]");
+  int shift = 0;
+  while ((int64_t(1) << shift) < block) ++shift;
+  return PackedView{data.data_ptr(), scales.data_ptr<float>(), nb * block, nb,
+                    shift, DELTA_I8};
+}
+
+void check_plane(const Tensor& t, int64_t P, const char* name) {
+  check_f32(t, name);
+  TORCH_CHECK(t.numel() == P, name, " must have P elements");
+  TORCH_CHECK(aligned16(t), name, " must be 16-byte aligned");
+}
+
+void weighted_merge_packed(Tensor base, Tensor data, Tensor scales,
+                           int64_t block, Tensor W, Tensor offsets,
+                           Tensor out) {
+  const int64_t P = base.numel();
+  check_plane(base, P, "base"); check_plane(out, P, "out");
+  const PackedView d = packed_view(data, scales, P, block);
+  const int n_models = int(data.size(0));
+  const int n_segs = int(offsets.numel() - 1);
+  TORCH_CHECK(n_segs >= 1 && W.dim() == 2 && W.size(0) == n_models &&
+                  W.size(1) == n_segs, "W must be [n_models, n_segs]");
+  TORCH_CHECK(dta_merge_shmem(n_models, n_segs) <= DTA_MERGE_LDS_LIMIT,
+              "offsets + W ([", n_models, ", ", n_segs,
+              "]) do not fit the LDS budget of ", DTA_MERGE_LDS_LIMIT, " B");
+  auto Wc = W.to(base.device(), torch::kFloat32).contiguous();
+  auto offs = offsets.to(base.device(), torch::kInt64).contiguous();
+  launch_weighted_merge_packed(base.data_ptr<float>(), d,
+                               Wc.data_ptr<float>(),
+                               offs.data_ptr<int64_t>(), n_models, n_segs, P,
+                               out.data_ptr<float>(), stream());
+}
+
+Tensor grad_merge_weights_packed(Tensor g, Tensor base, Tensor data,
+                                 Tensor scales, int64_t block, Tensor merged,
+                                 Tensor offsets) {
+  const int64_t P = base.numel();
+  check_plane(base, P, "base"); check_plane(merged, P, "merged");
+  const bool gb = g.scalar_type() == torch::kBFloat16;
+  TORCH_CHECK(g.is_cuda() && g.is_contiguous() && g.numel() == P &&
+                  (gb || g.scalar_type() == torch::kFloat32) && aligned16(g),
+              "g must be a contiguous 16-byte aligned bf16/fp32 [P] GPU "
+              "tensor");
+  const PackedView d = packed_view(data, scales, P, block);
+  const int n_models = int(data.size(0));
+  const int n_segs = int(offsets.numel() - 1);
+  TORCH_CHECK(n_segs >= 1, "offsets must be [n_segs + 1]");
+  auto ch = grad_w_chunks(offsets, base, n_segs);
+  const int n_chunks = int(ch.numel() / 3);
+  auto gw = torch::zeros({n_models, n_segs},
+                         base.options().dtype(torch::kFloat32));
+  launch_grad_merge_weights_packed(g.data_ptr(), gb, base.data_ptr<float>(),
+                                   d, merged.data_ptr<float>(),
+                                   ch.data_ptr<int64_t>(), n_models, n_chunks,
+                                   P, gw.data_ptr<float>(), n_segs, stream());
+  return gw;
+}
+
+void axpy_packed(Tensor w, Tensor data, Tensor scales, int64_t block,
+                 int64_t row, double alpha) {
+  const int64_t P = w.numel();
+  check_plane(w, P, "w");
+  const PackedView d = packed_view(data, scales, P, block);
+  TORCH_CHECK(row >= 0 && row < data.size(0), "row out of range");
+  launch_axpy_packed(w.data_ptr<float>(), d, int(row), float(alpha), P,
+                     stream());
+}
+
+// (codes [nb*block] int8, scales [nb] fp32) of x - base, or of x when base
+// is empty
+std::vector<Tensor> quantize_int8(Tensor x, Tensor base, int64_t block) {
+  check_f32(x, "x");
+  const int64_t P = x.numel();
+  TORCH_CHECK(P >= 1, "quantize_int8: empty input");
+  TORCH_CHECK(aligned16(x), "x must be 16-byte aligned");
+  TORCH_CHECK(block >= DTA_QUANT_MIN_BLOCK && block <= DTA_QUANT_MAX_BLOCK &&
+                  (block & (block - 1)) == 0,
+              "block must be a power of two in [", DTA_QUANT_MIN_BLOCK, ", ",
+              DTA_QUANT_MAX_BLOCK, "]");
+  const float* bp = nullptr;
+  if (base.numel()) {
+    check_plane(base, P, "base");
+    bp = base.data_ptr<float>();
+  }
+  const int64_t nb = (P + block - 1) / block;
+  TORCH_CHECK(nb < (int64_t(1) << 31), "too many quantisation blocks");
+  auto codes = torch::empty({nb * block}, x.options().dtype(torch::kInt8));
+  auto scales = torch::empty({nb}, x.options());
+  launch_delta_quantize_int8(x.data_ptr<float>(), bp, P, int(block), nb,
+                             reinterpret_cast<signed char*>(codes.data_ptr()),
+                             scales.data_ptr<float>(), stream());
+  return {codes, scales};
 }
 
 // ---- CE --------------------------------------------------------------------
@@ -840,6 +972,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("colsum", &colsum);
   m.def("weighted_merge", &weighted_merge);
   m.def("grad_merge_weights", &grad_merge_weights);
+  m.def("weighted_merge_packed", &weighted_merge_packed);
+  m.def("grad_merge_weights_packed", &grad_merge_weights_packed);
+  m.def("axpy_packed", &axpy_packed);
+  m.def("quantize_int8", &quantize_int8);
   m.def("ce_fwd", &ce_fwd);
   m.def("ce_bwd", &ce_bwd);
   m.def("ce_fwd_bwd", &ce_fwd_bwd, pybind11::arg("logits"),

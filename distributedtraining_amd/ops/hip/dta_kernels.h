@@ -100,6 +100,49 @@ void launch_grad_merge_weights(const void* g, bool g_is_bf16,
                                int n_models, int n_chunks, int64_t P,
                                float* grad_w,  // [N,S] pre-zeroed
                                int n_segs, hipStream_t s);
+// Gathered deltas kept in their wire form. bf16: data [N, ld = P]. int8:
+// data [N, ld = nb*block] codes, scales [N, nb] fp32, block == 1 << shift;
+// element e of row i is float(code) * scales[i, e >> shift], one rounded
+// fp32 multiply. The packed kernels produce what the fp32 ones produce on
+// the dequantised rows, bit for bit (grad_W keeps the fp32 kernel's
+// summation order). Merge and axpy read 4 elements per lane: base/out/w must
+// be 16 B aligned and data 8 B; bf16 with P % 4 != 0 falls back to one
+// element per lane.
+enum DeltaKind { DELTA_F32 = 0, DELTA_BF16 = 1, DELTA_I8 = 2 };
+struct PackedView {
+  const void* data;
+  const float* scales;   // int8 only
+  int64_t ld;            // elements per row of data
+  int64_t nb;            // scales per row (int8 only)
+  int shift;             // log2(block) (int8 only)
+  int kind;              // DeltaKind
+};
+constexpr int DTA_MERGE_MAX_MODELS = 32;   // miners per node (8 GPUs typical)
+constexpr size_t DTA_MERGE_LDS_LIMIT = 64 * 1024;   // offsets + W, per block
+// dynamic LDS weighted_merge needs for its offsets and W cache
+size_t dta_merge_shmem(int n_models, int n_segs);
+void launch_weighted_merge_packed(const float* base, const PackedView& d,
+                                  const float* W, const int64_t* offsets,
+                                  int n_models, int n_segs, int64_t P,
+                                  float* out, hipStream_t s);
+void launch_grad_merge_weights_packed(const void* g, bool g_is_bf16,
+                                      const float* base, const PackedView& d,
+                                      const float* merged,
+                                      const int64_t* chunks, int n_models,
+                                      int n_chunks, int64_t P, float* grad_w,
+                                      int n_segs, hipStream_t s);
+// w += alpha * row `row` of d, dequantised in registers
+void launch_axpy_packed(float* w, const PackedView& d, int row, float alpha,
+                        int64_t P, hipStream_t s);
+// Blockwise int8 of d = w - base (base null: of w), bit-equal to
+// comm.quantize_blockwise_int8 on the CPU. codes [nb*block], scales [nb],
+// nb = ceil(P / block); block a power of two in [DTA_QUANT_MIN_BLOCK,
+// DTA_QUANT_MAX_BLOCK]; w, base and codes 16 B aligned.
+constexpr int DTA_QUANT_MIN_BLOCK = 16;
+constexpr int DTA_QUANT_MAX_BLOCK = 16384;
+void launch_delta_quantize_int8(const float* w, const float* base, int64_t P,
+                                int block, int64_t nb, signed char* codes,
+                                float* scales, hipStream_t s);
 
 // ---- norms ----------------------------------------------------------------
 // dγ/dβ partial-panel geometry: for cols <= 1024 the partials come from

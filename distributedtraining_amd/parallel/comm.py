@@ -20,7 +20,8 @@ from __future__ import annotations
 
 import datetime
 import os
-from typing import List, Optional
+from dataclasses import dataclass
+from typing import List, Optional, Tuple
 
 import torch
 import torch.distributed as dist
@@ -45,6 +46,84 @@ def dequantize_blockwise_int8(q: torch.Tensor, scale: torch.Tensor,
                               numel: int, block: int = 4096) -> torch.Tensor:
     x = q.view(-1, block).to(torch.float32) * scale.unsqueeze(1)
     return x.view(-1)[:numel]
+
+
+@dataclass
+class PackedDeltas:
+    """N gathered deltas kept in their wire form (the resident gather under
+    ``comm.resident_dtype = "wire"``).
+
+    ``kind`` "fp32" / "bf16": ``data`` is [N, P]. ``kind`` "int8": ``data``
+    is [N, nb*block] codes and ``scales`` [N, nb] fp32 (the layout of
+    :func:`quantize_blockwise_int8`, one row per rank). ``numel`` is P.
+
+    ``ops.weighted_merge``, ``ops.grad_merge_weights`` and ``ops.axpy_``
+    take the container where they take an [N, P] tensor and dequantise in
+    registers; their results equal the tensor path on :meth:`dequantize`.
+    """
+
+    kind: str
+    data: torch.Tensor
+    numel: int
+    scales: Optional[torch.Tensor] = None
+    block: int = 4096
+
+    def __post_init__(self):
+        if self.kind not in ("fp32", "bf16", "int8"):
+            raise ValueError(f"unknown PackedDeltas kind {self.kind!r}")
+        want = {"fp32": torch.float32, "bf16": torch.bfloat16,
+                "int8": torch.int8}[self.kind]
+        if self.data.dim() != 2 or self.data.dtype != want:
+            raise ValueError(f"{self.kind} deltas need a 2-d {want} tensor")
+        if self.kind == "int8":
+            nb = (self.numel + self.block - 1) // self.block
+            if self.scales is None or self.data.shape[1] != nb * self.block \
+                    or tuple(self.scales.shape) != (self.data.shape[0], nb):
+                raise ValueError("int8 deltas need codes [N, nb*block] and "
+                                 "scales [N, nb]")
+        elif self.data.shape[1] != self.numel:
+            raise ValueError(f"{self.kind} deltas must be [N, numel]")
+
+    @classmethod
+    def pack(cls, deltas: torch.Tensor, kind: str,
+             block: int = 4096) -> "PackedDeltas":
+        """Compress an [N, P] fp32 stack row by row (tests, tools)."""
+        from .. import ops
+        n, P = deltas.shape
+        if kind == "fp32":
+            return cls("fp32", deltas.to(torch.float32).contiguous(), P)
+        if kind == "bf16":
+            return cls("bf16", deltas.to(torch.bfloat16).contiguous(), P)
+        rows = [ops.quantize_blockwise_int8(deltas[i].contiguous(), block)
+                for i in range(n)]
+        return cls("int8", torch.stack([q for q, _ in rows]), P,
+                   torch.stack([s for _, s in rows]), block)
+
+    @property
+    def shape(self) -> Tuple[int, int]:
+        return (self.data.shape[0], self.numel)
+
+    @property
+    def device(self) -> torch.device:
+        return self.data.device
+
+    def row(self, i: int) -> torch.Tensor:
+        """Row ``i`` as a fresh fp32 [P] tensor — the only O(P) temporary a
+        consumer of packed deltas may make."""
+        from .. import ops
+        if self.kind == "int8":
+            return ops.dequantize_blockwise_int8(
+                self.data[i], self.scales[i], self.numel, self.block)
+        if self.kind == "bf16" and ops.use_hip(self.data):
+            out = torch.zeros(self.numel, dtype=torch.float32,
+                              device=self.data.device)
+            return ops.axpy_(out, (self, i), 1.0)
+        return self.data[i].to(torch.float32, copy=True)
+
+    def dequantize(self) -> torch.Tensor:
+        """[N, P] fp32 — for tests and small planes; at model scale this is
+        the footprint the container exists to avoid."""
+        return torch.stack([self.row(i) for i in range(self.shape[0])])
 
 
 class CommPlane:
@@ -88,9 +167,12 @@ class CommPlane:
                         ) -> torch.Tensor:
         """Gather each rank's flat tensor -> [world, P] (every rank gets all
         deltas, HBM-resident). ``wire_dtype`` (e.g. torch.bfloat16) halves
-        the xGMI bytes AND the resident gather footprint — 8 fp32
-        Llama-3-8B deltas are 256 GB (impossible), 8 bf16 are 128 GB (fits
-        in 288 GB HBM3E); the merge math upcasts per element."""
+        the xGMI bytes and the tensor returned here — 8 fp32 Llama-3-8B
+        deltas are 256 GB (impossible), 8 bf16 are 128 GB (fits in 288 GB
+        HBM3E). The gather STAYS that small only under
+        ``comm.resident_dtype = "wire"`` (:meth:`all_gather_packed`: the
+        merge kernels upcast per element); the default path casts the
+        whole gather back to fp32 next to it."""
         if not self.is_distributed:
             return (flat if wire_dtype is None
                     else flat.to(wire_dtype)).unsqueeze(0)
@@ -114,11 +196,13 @@ class CommPlane:
     def all_gather_flat_int8(self, flat: torch.Tensor, block: int = 4096
                              ) -> torch.Tensor:
         """All-gather with blockwise-int8 wire compression: 4x fewer xGMI
-        bytes AND a 4x smaller resident gather than fp32 (8 Llama-3-8B
-        deltas: 64 GB int8 vs 256 GB fp32). Per-block absmax scaling keeps
-        the worst-case element error <= absmax(block)/127; weight DELTAS
-        (small, zero-centered) tolerate this — the merge math runs fp32 on
-        the dequantized rows. Returns [world, P] fp32."""
+        bytes than fp32. Per-block absmax scaling keeps the worst-case
+        element error <= absmax(block)/127; weight DELTAS (small,
+        zero-centered) tolerate this — the merge math runs fp32 on the
+        dequantized rows. Returns [world, P] fp32: the RESIDENT gather is
+        as large as an fp32 one. :meth:`all_gather_packed`
+        (``comm.resident_dtype = "wire"``) keeps it int8 — 8 Llama-3-8B
+        deltas: 64 GB against 256 GB."""
         q, scale = quantize_blockwise_int8(flat, block)
         qg = self.all_gather_flat(q)          # [world, nb*block] int8
         sg = self.all_gather_flat(scale)      # [world, nb] fp32
@@ -126,6 +210,30 @@ class CommPlane:
         return torch.stack([
             dequantize_blockwise_int8(qg[r], sg[r], n, block)
             for r in range(qg.shape[0])])
+
+    def all_gather_packed(self, flat: torch.Tensor, kind: str,
+                          block: int = 4096,
+                          base: Optional[torch.Tensor] = None
+                          ) -> PackedDeltas:
+        """Gather every rank's delta and KEEP it in wire form. The delta is
+        ``flat``, or ``flat - base`` when ``base`` is given (int8 then
+        quantises straight from the two planes in one kernel and the fp32
+        delta is never written). int8: the two gathers of
+        :meth:`all_gather_flat_int8`; bf16: one cast, one gather."""
+        from .. import ops
+        n = flat.numel()
+        if kind == "int8":
+            q, scale = ops.quantize_blockwise_int8(flat, block, base=base)
+            return PackedDeltas("int8", self.all_gather_flat(q), n,
+                                self.all_gather_flat(scale), block)
+        if base is not None:
+            flat = ops.delta_sub(flat, base)
+        if kind == "bf16":
+            return PackedDeltas(
+                "bf16", self.all_gather_flat(flat, torch.bfloat16), n)
+        if kind != "fp32":
+            raise ValueError(f"unknown wire kind {kind!r}")
+        return PackedDeltas("fp32", self.all_gather_flat(flat), n)
 
     # -- C2/C5: base publication --------------------------------------------
     def broadcast_flat(self, flat: torch.Tensor, src: int = 0) -> torch.Tensor:

@@ -10,7 +10,8 @@ miner→HF-hub→averager→HF-hub→miner round trip.
 Collective choice per strategy (see merge_round): mean/nesterov use an
 all-reduce (O(P) resident — mandatory at Llama scale); score-weighted,
 meta-learned and genetic use an all-gather (every delta HBM-resident,
-optionally bf16/int8 on the wire). Deterministic merges are computed
+optionally bf16/int8 on the wire, and with comm.resident_dtype = "wire"
+also bf16/int8 in HBM). Deterministic merges are computed
 redundantly by every rank (identical bases, no broadcast); the
 meta-learned and genetic merges run on rank 0 (they need val-loss
 evaluations) and are broadcast (C2/C5).
@@ -24,7 +25,7 @@ from typing import Dict, List, Optional
 import torch
 
 from ..config import Config
-from ..parallel.comm import CommPlane
+from ..parallel.comm import CommPlane, PackedDeltas
 from ..parallel.flat import FlatParams
 from ..roles.averager import ParameterizedAverager
 from ..roles.miner import DeltaLoop
@@ -60,9 +61,32 @@ class LocalSGDNode:
         return (torch.bfloat16 if self.cfg.comm.exchange_dtype == "bf16"
                 else None)
 
-    def _gather_deltas(self, flat: torch.Tensor) -> torch.Tensor:
-        """All-gather the flat delta at the configured wire dtype; always
-        returns [world, P] fp32 for the merge math."""
+    def _resident_wire(self) -> bool:
+        rd = self.cfg.comm.resident_dtype
+        if rd not in ("fp32", "wire"):
+            raise ValueError(f"unknown comm.resident_dtype {rd!r}")
+        return rd == "wire"
+
+    def _local_delta(self, base: torch.Tensor) -> Optional[torch.Tensor]:
+        """This rank's fp32 delta for the gather — None where the gather
+        quantises straight from fp.master and base instead (int8 kept in
+        wire form: make_delta's fp32 plane is never written)."""
+        if self._resident_wire() and self.cfg.comm.exchange_dtype == "int8":
+            return None
+        return self.fp.make_delta(base).flat    # fused θ−θ_base
+
+    def _gather_deltas(self, flat: Optional[torch.Tensor],
+                       base: Optional[torch.Tensor] = None):
+        """All-gather the flat delta at the configured wire dtype. Returns
+        [world, P] fp32 for the merge math, or under comm.resident_dtype =
+        "wire" a PackedDeltas still in wire form. ``flat`` None (see
+        _local_delta): the delta is fp.master − ``base``."""
+        if self._resident_wire():
+            if flat is None:
+                return self.comm.all_gather_packed(
+                    self.fp.master, "int8", base=base)
+            return self.comm.all_gather_packed(
+                flat, self.cfg.comm.exchange_dtype)
         if self.cfg.comm.exchange_dtype == "int8":
             return self.comm.all_gather_flat_int8(flat)
         return self.comm.all_gather_flat(flat, self._wire_dtype()) \
@@ -87,11 +111,12 @@ class LocalSGDNode:
           (required for Llama-3-8B x 8 ranks: a gather would need 256 GB);
         * score_weighted/parameterized/genetic: all-gather, all deltas
           HBM-resident (8 fp32 GPT-2 deltas ≈ 4 GB — the scoring/meta/
-          evolutionary paths need every delta individually)."""
+          evolutionary paths need every delta individually); with
+          comm.resident_dtype = "wire" they stay bf16/int8 in HBM."""
         base = self.miner.base
-        delta = self.fp.make_delta(base)     # fused θ−θ_base
         strat = self.merge_strategy
         if strat in ("mean", "uniform", "nesterov"):
+            delta = self.fp.make_delta(base)     # fused θ−θ_base
             d = self.comm.all_reduce_mean(delta.flat)
             if strat == "nesterov":
                 merged = self.averager.nesterov_merge(base, d.unsqueeze(0))
@@ -100,10 +125,11 @@ class LocalSGDNode:
         elif strat == "score_weighted":
             assert scores is not None
             merged = self.averager.score_weighted_merge(
-                base, self._gather_deltas(delta.flat), scores)
+                base, self._gather_deltas(self._local_delta(base), base),
+                scores)
         elif strat in ("parameterized", "genetic"):
             # both need val-loss evaluations: run on rank 0, broadcast
-            deltas = self._gather_deltas(delta.flat)
+            deltas = self._gather_deltas(self._local_delta(base), base)
             if self.comm.rank == 0:
                 merged = (self.averager.meta_learning(base, deltas,
                                                       self.val_batches)
@@ -144,18 +170,26 @@ class LocalSGDNode:
         loop (validation_logic.py:126-139). Normalization happens
         identically on every rank from the gathered totals."""
         base = self.miner.base
-        delta = self.fp.make_delta(base)
-        deltas = self.comm.all_gather_flat(delta.flat)
+        if self._resident_wire():
+            # the configured wire dtype applies to validation too, and the
+            # gather stays in that form (rows are applied by ops.axpy_)
+            deltas = self._gather_deltas(self._local_delta(base), base)
+        else:
+            delta = self.fp.make_delta(base)
+            deltas = self.comm.all_gather_flat(delta.flat)
         saved = self.fp.master.clone()
         self.fp.load_flat_master(base)   # score against the base, not the
         validator = self._refresh_validator()   # locally-drifted weights
         my: Dict[str, float] = {}
         N = deltas.shape[0]
         for i in range(self.comm.rank, N, self.comm.world_size):
-            ck = DeltaCheckpoint(deltas[i].to(torch.float32), self.fp.spec,
-                                 "")
             try:
-                _, _, _, ppl_score = validator.score_delta(ck)
+                if isinstance(deltas, PackedDeltas):
+                    _, _, _, ppl_score = validator.score_packed(deltas, i)
+                else:
+                    ck = DeltaCheckpoint(deltas[i].to(torch.float32),
+                                         self.fp.spec, "")
+                    _, _, _, ppl_score = validator.score_delta(ck)
             except Exception as e:   # reference: per-miner failure → 0
                 log.warning("rank%d scoring failed (%s), score 0", i, e)
                 ppl_score = 0.0

@@ -122,6 +122,29 @@ class DeltaValidator:
         ppl_score = max(0.0, self.base_perplexity - ppl)
         return loss, ppl, loss_score, ppl_score
 
+    def score_packed(self, deltas, i: int) -> Tuple[float, float, float, float]:
+        """score_delta for row ``i`` of a PackedDeltas (a gather kept in
+        wire form): θ += δ_i is applied straight from the packed row
+        (ops.axpy_), so no fp32 copy of the delta exists. A NaN in the row
+        (a NaN int8 scale, a NaN bf16 element) reaches θ and is rejected
+        there."""
+        if deltas.shape[1] != self.fp.numel:
+            log.warning("shape-mismatch delta rejected")
+            return 1e8, 1e8, 0.0, 0.0
+        saved = self.fp.master.clone()
+        ops.axpy_(self.fp.master, (deltas, i), 1.0)
+        if ops.has_nan(self.fp.master):
+            log.warning("NaN delta rejected")
+            self.fp.master.copy_(saved)
+            return 1e8, 1e8, 0.0, 0.0
+        self.fp.sync_work_from_master()
+        loss, ppl = self.evaluate_model()
+        self.fp.master.copy_(saved)
+        self.fp.sync_work_from_master()
+        loss_score = max(0.0, self.base_loss - loss)
+        ppl_score = max(0.0, self.base_perplexity - ppl)
+        return loss, ppl, loss_score, ppl_score
+
     # -- full round (reference :99-189) ---------------------------------------
     def validate_and_score(
             self, deltas: Optional[Dict[str, Optional[DeltaCheckpoint]]] = None
