@@ -98,7 +98,7 @@ class _LinearFn(torch.autograd.Function):
             dw = None
         else:
             dw = dy2.t().mm(x2)
-        db = (_grad_out(m.colsum(dy2), ctx.bgrad, w.dtype)
+        db = (_cast_grad(m.colsum(dy2, ctx.bgrad), w.dtype)
               if ctx.has_b else None)
         return dx, dw, db
 
@@ -179,7 +179,7 @@ class _FusedMLPFn(torch.autograd.Function):
         dy2 = dy.reshape(-1, dy.shape[-1])
         if dy2.stride(-1) != 1:
             dy2 = dy2.contiguous()
-        db2 = _grad_out(m.colsum(dy2), ctx.b2grad, w2.dtype)
+        db2 = _cast_grad(m.colsum(dy2, ctx.b2grad), w2.dtype)
         if ctx.w2grad is not None:
             ctx.w2grad.addmm_(dy2.t(), h)
             dw2 = None
@@ -195,12 +195,71 @@ class _FusedMLPFn(torch.autograd.Function):
         return dx, dw1, db1, dw2, db2
 
 
+# DTA_MLP_NODE=0 keeps the composed path on linear -> gelu -> linear, three
+# autograd nodes with a separate colsum over dh_pre for the fc bias.
+_MLP_NODE = _os.environ.get("DTA_MLP_NODE", "1") != "0"
+
+
+def mlp_node_enable(on: bool) -> bool:
+    """Switch the one-node composed MLP (tests flip it in one process).
+    Returns the previous setting."""
+    global _MLP_NODE
+    prev, _MLP_NODE = _MLP_NODE, bool(on)
+    return prev
+
+
+class _MLPGeluFn(torch.autograd.Function):
+    """The composed GPT-2 MLP as one node: the GEMMs, their operands and the
+    saved tensors of linear -> gelu -> linear, with the fc bias gradient
+    summed by the kernel that writes dh_pre (gelu_bwd_colsum) instead of a
+    second pass over it. bf16 only."""
+
+    @staticmethod
+    def forward(ctx, x, w1, b1, w2, b2):
+        m = require_ext()
+        x2 = x.reshape(-1, x.shape[-1])
+        pre = torch.addmm(b1, x2, w1.t())
+        h = m.gelu_fwd(pre)
+        y = torch.addmm(b2, h, w2.t())
+        ctx.save_for_backward(x2, w1, w2, pre, h)
+        ctx.xshape = x.shape
+        ctx.grads = tuple(getattr(t, "main_grad", None)
+                          for t in (w1, b1, w2, b2))
+        return y.view(*x.shape[:-1], w2.shape[0])
+
+    @staticmethod
+    def backward(ctx, dy):
+        m = require_ext()
+        x2, w1, w2, pre, h = ctx.saved_tensors
+        w1g, b1g, w2g, b2g = ctx.grads
+        dy2 = dy.reshape(-1, dy.shape[-1])
+        if dy2.stride(-1) != 1:
+            dy2 = dy2.contiguous()
+        dh = dy2.mm(w2)
+        if w2g is not None:
+            w2g.addmm_(dy2.t(), h)
+            dw2 = None
+        else:
+            dw2 = dy2.t().mm(h)
+        db2 = _cast_grad(m.colsum(dy2, b2g), w2.dtype)
+        dh_pre, db1 = m.gelu_bwd_colsum(dh, pre, b1g)
+        del dh
+        dx = dh_pre.mm(w1).view(ctx.xshape)
+        if w1g is not None:
+            w1g.addmm_(dh_pre.t(), x2)
+            dw1 = None
+        else:
+            dw1 = dh_pre.t().mm(x2)
+        return dx, dw1, _cast_grad(db1, w1.dtype), dw2, db2
+
+
 def mlp_gelu(x: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor,
              w2: torch.Tensor, b2: torch.Tensor) -> torch.Tensor:
     """y = gelu(x W1ᵀ + b1) W2ᵀ + b2 (GPT-2 MLP). On GPU, epilogue-fused
     via hipBLASLt when available for this (M, N, K); shapes the epilogue
-    heuristics reject fall back to the composed ops path (cached, logged
-    once per shape)."""
+    heuristics reject fall back to the composed path (cached, logged
+    once per shape): one autograd node for bf16 (_MLPGeluFn), else
+    linear -> gelu -> linear."""
     if use_hip(x):
         rows = x.numel() // x.shape[-1]
         if rows <= 4 and not torch.is_grad_enabled():
@@ -218,6 +277,9 @@ def mlp_gelu(x: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor,
                     "hipBLASLt epilogue MLP unavailable at M,N,K=%s (%s); "
                     "composed path", key, e)
                 _lt_fused_shape_ok[key] = False
+        if _MLP_NODE and all(t.dtype == torch.bfloat16
+                             for t in (x, w1, b1, w2, b2)):
+            return _MLPGeluFn.apply(x, w1, b1, w2, b2)
         return linear(gelu(linear(x, w1, b1)), w2, b2)
     return F.linear(F.gelu(F.linear(x, w1, b1), approximate="tanh"), w2, b2)
 
@@ -236,11 +298,19 @@ def _rng0(t: torch.Tensor) -> torch.Tensor:
 def _grad_out(fp32_grad, main_grad, dtype):
     """Deliver a parameter gradient: accumulate the fp32 reduction into
     the flat bf16 grad plane when the param carries one (single fused
-    kernel), else hand autograd a cast tensor (plain-module models)."""
+    kernel), else hand autograd a cast tensor (plain-module models).
+    Only for producers without a finisher of their own (the embeddings):
+    the column reductions take main_grad as their destination."""
     if main_grad is not None:
         require_ext().accum_f32_into_bf16(main_grad, fp32_grad)
         return None
     return fp32_grad.to(dtype)
+
+
+def _cast_grad(fp32_grad, dtype):
+    """What a column reduction hands autograd: None where it accumulated
+    into main_grad itself, else the fp32 result cast to the param dtype."""
+    return None if fp32_grad is None else fp32_grad.to(dtype)
 
 
 def _cpu_drop(t: torch.Tensor, p: float, site: int) -> torch.Tensor:
@@ -261,14 +331,15 @@ def _norm_fwd(x2, res, w, b, eps, site, p):
     return y, (mean, rstd), s
 
 
-def _norm_bwd(dy, ds, x2, w, stats, site, p):
-    """-> (dx, dw32, db32 or None, dres)."""
+def _norm_bwd(dy, ds, x2, w, stats, site, p, wg=None, bg=None):
+    """-> (dx, dw32, db32 or None, dres). wg/bg: main_grad views dγ/dβ are
+    accumulated into by the kernel itself; that fp32 result is then None."""
     m = require_ext()
     if len(stats) == 1:
         dx, dw32, dres = m.rmsnorm_bwd(dy, ds, x2, w, *stats, _rng0(x2),
-                                       site, p)
+                                       site, p, wg)
         return dx, dw32, None, dres
-    return m.layernorm_bwd(dy, ds, x2, w, *stats, _rng0(x2), site, p)
+    return m.layernorm_bwd(dy, ds, x2, w, *stats, _rng0(x2), site, p, wg, bg)
 
 
 class _NormFn(torch.autograd.Function):
@@ -288,10 +359,9 @@ class _NormFn(torch.autograd.Function):
         N = x.shape[-1]
         dx, dw32, db32, _ = _norm_bwd(dy.contiguous().view(-1, N),
                                       _empty_like0(x), x.view(-1, N), w,
-                                      stats, 0, 0.0)
-        return (dx.view_as(x), _grad_out(dw32, ctx.wg, w.dtype),
-                None if db32 is None else _grad_out(db32, ctx.bg, w.dtype),
-                None)
+                                      stats, 0, 0.0, ctx.wg, ctx.bg)
+        return (dx.view_as(x), _cast_grad(dw32, w.dtype),
+                _cast_grad(db32, w.dtype), None)
 
 
 def layer_norm(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor,
@@ -334,11 +404,11 @@ class _AddNormFn(torch.autograd.Function):
         ds2 = (ds.contiguous().view(-1, N) if ds is not None
                else _empty_like0(s))
         dx, dw32, db32, dres = _norm_bwd(dy.contiguous().view(-1, N), ds2, s,
-                                         w, stats, site, p_drop)
+                                         w, stats, site, p_drop, ctx.wg,
+                                         ctx.bg)
         dx = dx.view(ctx.shape)
         dr = dres.view(ctx.shape) if p_drop > 0.0 else dx
-        return (dx, dr, _grad_out(dw32, ctx.wg, w.dtype),
-                None if db32 is None else _grad_out(db32, ctx.bg, w.dtype),
+        return (dx, dr, _cast_grad(dw32, w.dtype), _cast_grad(db32, w.dtype),
                 None, None, None)
 
 

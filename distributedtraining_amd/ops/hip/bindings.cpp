@@ -51,6 +51,18 @@ DropParams drop_params(const Tensor& rng, int64_t site, double p) {
   return d;
 }
 
+// ---- column-reduction destinations -----------------------------------------
+// Optional trailing argument of colsum / *norm_bwd / gelu_bwd_colsum: a bf16
+// [cols] gradient view (a flat-plane slice, any alignment) the reduction
+// accumulates into instead of returning an fp32 tensor.
+using OptTensor = c10::optional<Tensor>;
+bf16_t* grad_dst(OptTensor& d, int64_t cols, const char* name) {
+  if (!d.has_value() || !d->defined()) return nullptr;
+  check_bf16(*d, name);
+  TORCH_CHECK(d->numel() == cols, name, " must have cols elements");
+  return bfp_mut(*d);
+}
+
 // ---- norms ----------------------------------------------------------------
 // LayerNorm and RMSNorm share one implementation per direction; b == null
 // selects RMSNorm (no bias, no mean).
@@ -94,10 +106,12 @@ std::vector<Tensor> norm_fwd(Tensor x, Tensor res, Tensor w, const Tensor* b,
 // stream, folded into dx (dx = ds + dNorm/dx). p > 0: also emits
 // dres = dx ⊙ mask/(1-p) for the dropped branch.
 // Returns {dx, dw32, db32 (undefined for RMS), dres}; fp32 grads: the ops
-// layer accumulates or casts.
+// layer casts. dw_dst / db_dst: accumulate that gradient into the bf16
+// destination instead (its fp32 tensor is then undefined).
 std::vector<Tensor> norm_bwd(Tensor dy, Tensor ds, Tensor x, Tensor w,
                              const Tensor* mean, Tensor rstd, Tensor rng,
-                             int64_t site, double p) {
+                             int64_t site, double p, OptTensor dw_dst,
+                             OptTensor db_dst) {
   const int cols = norm_cols(x, DTA_NORM_BWD_MAX_COLS, "norm backward");
   check_bf16(dy, "dy"); check_bf16(w, "w");
   const int64_t rows = x.size(0);
@@ -108,18 +122,21 @@ std::vector<Tensor> norm_bwd(Tensor dy, Tensor ds, Tensor x, Tensor w,
   auto dres = drop.thr16 ? torch::empty_like(x)
                          : torch::empty({0}, x.options());
   const auto f32 = x.options().dtype(torch::kFloat32);
-  auto dw32 = torch::zeros({cols}, f32);
-  Tensor db32 = mean ? torch::zeros({cols}, f32) : Tensor();
+  bf16_t* dwd = grad_dst(dw_dst, cols, "dw_dst");
+  bf16_t* dbd = mean ? grad_dst(db_dst, cols, "db_dst") : nullptr;
+  Tensor dw32 = dwd ? Tensor() : torch::empty({cols}, f32);
+  Tensor db32 = (mean && !dbd) ? torch::empty({cols}, f32) : Tensor();
   const int stripes = dta_norm_bwd_stripes(rows, cols);
   auto part = torch::empty({mean ? 2 : 1, stripes, cols}, f32);
   launch_norm_bwd({bfp(dy), has_ds ? bfp(ds) : nullptr, bfp(x), bfp(w),
                    mean ? mean->data_ptr<float>() : nullptr,
                    rstd.data_ptr<float>(), bfp_mut(dx),
                    drop.thr16 ? bfp_mut(dres) : nullptr,
-                   dw32.data_ptr<float>(),
-                   mean ? db32.data_ptr<float>() : nullptr,
+                   dwd ? nullptr : dw32.data_ptr<float>(),
+                   db32.defined() ? db32.data_ptr<float>() : nullptr,
                    part[0].data_ptr<float>(),
-                   mean ? part[1].data_ptr<float>() : nullptr, stripes, rows,
+                   mean ? part[1].data_ptr<float>() : nullptr, dwd, dbd,
+                   stripes, rows,
                    cols, drop, !mean},
                   stream());
   return {dx, dw32, db32, dres};
@@ -132,8 +149,9 @@ std::vector<Tensor> layernorm_fwd(Tensor x, Tensor res, Tensor w, Tensor b,
 }
 std::vector<Tensor> layernorm_bwd(Tensor dy, Tensor ds, Tensor x, Tensor w,
                                   Tensor mean, Tensor rstd, Tensor rng,
-                                  int64_t site, double p) {
-  return norm_bwd(dy, ds, x, w, &mean, rstd, rng, site, p);
+                                  int64_t site, double p, OptTensor dw_dst,
+                                  OptTensor db_dst) {
+  return norm_bwd(dy, ds, x, w, &mean, rstd, rng, site, p, dw_dst, db_dst);
 }
 std::vector<Tensor> rmsnorm_fwd(Tensor x, Tensor res, Tensor w, double eps,
                                 Tensor rng, int64_t site, double p) {
@@ -142,8 +160,9 @@ std::vector<Tensor> rmsnorm_fwd(Tensor x, Tensor res, Tensor w, double eps,
 }
 std::vector<Tensor> rmsnorm_bwd(Tensor dy, Tensor ds, Tensor x, Tensor w,
                                 Tensor rstd, Tensor rng, int64_t site,
-                                double p) {
-  auto o = norm_bwd(dy, ds, x, w, nullptr, rstd, rng, site, p);
+                                double p, OptTensor dw_dst) {
+  auto o = norm_bwd(dy, ds, x, w, nullptr, rstd, rng, site, p, dw_dst,
+                    c10::nullopt);
   return {o[0], o[1], o[3]};  // dx, dw32, dres
 }
 
@@ -261,20 +280,52 @@ void adamw_tick(Tensor t, Tensor bc, double beta1, double beta2) {
                     stream());
 }
 
-// column sum of a [rows, cols] bf16 matrix -> fp32 [cols] (bias gradient)
-Tensor colsum(Tensor x) {
+// column sum of a [rows, cols] bf16 matrix -> fp32 [cols] (bias gradient),
+// or accumulated into dst (nothing returned)
+Tensor colsum(Tensor x, OptTensor dst) {
   check_bf16(x, "x");
-  TORCH_CHECK(x.dim() == 2 && x.size(1) % 8 == 0,
-              "x must be [rows, cols] with cols % 8 == 0");
+  TORCH_CHECK(x.dim() == 2 && x.size(1) >= 1, "x must be [rows, cols]");
   const int64_t rows = x.size(0);
   const int cols = int(x.size(1));
   const int stripes = dta_colred_stripes(rows, cols);
   auto f32 = x.options().dtype(torch::kFloat32);
-  auto part = torch::empty({stripes, cols}, f32);
-  auto out = torch::zeros({cols}, f32);
-  launch_colsum(bfp(x), part.data_ptr<float>(), out.data_ptr<float>(), rows,
-                cols, stripes, stream());
+  auto part = torch::empty({stripes, dta_colred_ld(cols)}, f32);
+  bf16_t* d = grad_dst(dst, cols, "dst");
+  Tensor out = d ? Tensor() : torch::empty({cols}, f32);
+  launch_colsum(bfp(x), part.data_ptr<float>(),
+                d ? nullptr : out.data_ptr<float>(), d, rows, cols, stripes,
+                stream());
   return out;
+}
+
+// {dx, db32}: dx = gelu_bwd(dy, x) bit for bit, db32 = colsum(dx) up to the
+// order of the fp32 sum, from one pass over [rows, cols] bf16 where
+// cols % 8 == 0 (else gelu_bwd then colsum). db_dst as colsum's dst.
+// stripes > 0 overrides the automatic row-stripe count (measurement only).
+std::vector<Tensor> gelu_bwd_colsum(Tensor dy, Tensor x, OptTensor db_dst,
+                                    int64_t stripes_arg) {
+  check_bf16(x, "x"); check_bf16(dy, "dy");
+  TORCH_CHECK(x.dim() == 2 && dy.sizes() == x.sizes(),
+              "dy, x must be [rows, cols]");
+  const int64_t rows = x.size(0);
+  const int cols = int(x.size(1));
+  if (cols % 8 != 0) {
+    auto dx = gelu_bwd(dy, x);
+    return {dx, colsum(dx, db_dst)};
+  }
+  const int stripes =
+      stripes_arg > 0 ? int(std::min<int64_t>(stripes_arg, 65535))
+                      : dta_gelu_colsum_stripes(rows, cols);
+  auto f32 = x.options().dtype(torch::kFloat32);
+  auto dx = torch::empty_like(x);
+  auto part = torch::empty({stripes, cols}, f32);
+  bf16_t* d = grad_dst(db_dst, cols, "db_dst");
+  Tensor out = d ? Tensor() : torch::empty({cols}, f32);
+  launch_gelu_bwd_colsum(bfp(dy), bfp(x), bfp_mut(dx),
+                         part.data_ptr<float>(),
+                         d ? nullptr : out.data_ptr<float>(), d, rows, cols,
+                         stripes, stream());
+  return {dx, out};
 }
 
 // ---- merge plane -----------------------------------------------------------
@@ -684,8 +735,10 @@ std::vector<Tensor> embedding_bwd(Tensor dy, Tensor ids, int64_t vocab,
     TORCH_CHECK(pcols % 8 == 0, "seq*dim must be a multiple of 8");
     const int stripes = dta_colred_stripes(B, pcols);
     auto part = torch::empty({stripes, pcols}, f32);
+    // stores dwpe[:pcols] (seq <= npos); the rows past seq stay zero
+    TORCH_CHECK(seq <= npos, "seq must be <= npos");
     launch_colsum(bfp(dy), part.data_ptr<float>(), dwpe.data_ptr<float>(),
-                  B, pcols, stripes, stream());
+                  nullptr, B, pcols, stripes, stream());
   }
   return {dwte, dwpe};  // fp32: ops layer accumulates or casts
 }
@@ -953,11 +1006,19 @@ void register_lt_fused(pybind11::module& m);  // lt_fused.cpp
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   register_lt_fused(m);
   m.def("layernorm_fwd", &layernorm_fwd);
-  m.def("layernorm_bwd", &layernorm_bwd);
+  namespace py = pybind11;
+  m.def("layernorm_bwd", &layernorm_bwd, py::arg("dy"), py::arg("ds"),
+        py::arg("x"), py::arg("w"), py::arg("mean"), py::arg("rstd"),
+        py::arg("rng"), py::arg("site"), py::arg("p"),
+        py::arg("dw_dst") = py::none(), py::arg("db_dst") = py::none());
   m.def("rmsnorm_fwd", &rmsnorm_fwd);
-  m.def("rmsnorm_bwd", &rmsnorm_bwd);
+  m.def("rmsnorm_bwd", &rmsnorm_bwd, py::arg("dy"), py::arg("ds"),
+        py::arg("x"), py::arg("w"), py::arg("rstd"), py::arg("rng"),
+        py::arg("site"), py::arg("p"), py::arg("dw_dst") = py::none());
   m.def("gelu_fwd", &gelu_fwd);
   m.def("gelu_bwd", &gelu_bwd);
+  m.def("gelu_bwd_colsum", &gelu_bwd_colsum, py::arg("dy"), py::arg("x"),
+        py::arg("db_dst") = py::none(), py::arg("stripes") = 0);
   m.def("swiglu_fwd", &swiglu_fwd);
   m.def("swiglu_bwd", &swiglu_bwd);
   m.def("dropout_apply", &dropout_apply);
@@ -969,7 +1030,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("l2norm_sq", &l2norm_sq);
   m.def("adamw_step", &adamw_step);
   m.def("adamw_tick", &adamw_tick);
-  m.def("colsum", &colsum);
+  m.def("colsum", &colsum, py::arg("x"), py::arg("dst") = py::none());
   m.def("weighted_merge", &weighted_merge);
   m.def("grad_merge_weights", &grad_merge_weights);
   m.def("weighted_merge_packed", &weighted_merge_packed);

@@ -63,8 +63,31 @@ void launch_adamw(float* master, const void* grad, bool grad_is_bf16,
                   float eps, float wd, int64_t n, hipStream_t s);
 void launch_adamw_tick(int* t, float* bc, double beta1, double beta2,
                        hipStream_t s);
-void launch_colsum(const bf16_t* x, float* part, float* out, int64_t rows,
-                   int cols, int stripes, hipStream_t s);
+// Column reductions run in two phases: a producer writes a [stripes, ld]
+// fp32 partial panel, launch_colred_finish folds it over the stripes in a
+// fixed order and writes every output once. Per panel k: dstk non-null
+// accumulates into a bf16 destination of any alignment,
+// dstk = bf16(float(dstk) + sum); else outk [cols] fp32 is stored (it need
+// not be zeroed). p1 null: one panel. ld % 4 == 0, cols <= ld.
+struct ColFinishArgs {
+  const float *p0, *p1;
+  float *out0, *out1;
+  bf16_t *dst0, *dst1;
+  int stripes, cols, ld;
+};
+void launch_colred_finish(const ColFinishArgs& a, hipStream_t s);
+// panel row length of launch_colsum: cols, padded to 4 where cols % 8 != 0
+// (those shapes take a one-column-per-lane producer)
+inline int dta_colred_ld(int cols) { return (cols + 3) / 4 * 4; }
+// out[c] (or dst[c] +=) sum_r x[r,c]; part: [stripes, dta_colred_ld(cols)]
+void launch_colsum(const bf16_t* x, float* part, float* out, bf16_t* dst,
+                   int64_t rows, int cols, int stripes, hipStream_t s);
+// dx = bf16(dy * gelu'(x)) and the column sums of dx in one pass over
+// [rows, cols], cols % 8 == 0; part: [stripes, cols]; out/dst as above
+void launch_gelu_bwd_colsum(const bf16_t* dy, const bf16_t* x, bf16_t* dx,
+                            float* part, float* out, bf16_t* dst,
+                            int64_t rows, int cols, int stripes,
+                            hipStream_t s);
 // launch config for the two-phase column reductions (colsum / norm dγdβ):
 // block sized to the active lane count (cols/8 threads, 64-multiple),
 // stripe count targeting ~512 blocks of 256-thread-equivalents.
@@ -73,7 +96,7 @@ inline ColRedCfg dta_colred_cfg(int64_t rows, int cols) {
   const int lanes = cols / 8;
   // balance lanes across gx blocks (a 256-thread split left trailing
   // blocks ~12% occupied at lanes=288, e.g. the qkv dbias shape)
-  const int gx = (lanes + 255) / 256;
+  const int gx = lanes > 0 ? (lanes + 255) / 256 : 1;   // cols < 8: one block
   int threads = ((lanes + gx - 1) / gx + 63) / 64 * 64;
   if (threads < 64) threads = 64;
   // target ~1024 blocks of 256-thread-equivalents (measured best; halving
@@ -86,6 +109,16 @@ inline ColRedCfg dta_colred_cfg(int64_t rows, int cols) {
 }
 inline int dta_colred_stripes(int64_t rows, int cols) {
   return dta_colred_cfg(rows, cols).stripes;
+}
+// row stripes of launch_gelu_bwd_colsum: 1.5 x the colsum value. Its loop
+// body is ~10x longer per row than colsum_part_k's, and at [65536, 3072]
+// the 682 stripes of dta_colred_cfg are 4 waves per SIMD: measured 0.301 ms
+// there, 0.283 at 1024, 0.281 at 2048 (tools/bias_grad_ab.py
+// --gelu-stripes), against 4 MB more panel per 341 stripes.
+inline int dta_gelu_colsum_stripes(int64_t rows, int cols) {
+  const int64_t st = int64_t(dta_colred_stripes(rows, cols)) * 3 / 2;
+  const int64_t mx = (rows + 31) / 32;
+  return int(st > mx ? (mx > 0 ? mx : 1) : st);
 }
 
 // ---- merge plane ----------------------------------------------------------
@@ -196,13 +229,16 @@ struct NormFwdArgs {
   bool rms;
 };
 // pdw/pdb: [stripes, cols] fp32 workspaces (dta_norm_bwd_stripes rows) of
-// the two-phase dγ/dβ column reduction; its second phase finishes with
-// atomicAdd into the pre-zeroed dw/db, so they do not repeat bit for bit.
+// the two-phase dγ/dβ column reduction; launch_colred_finish folds them
+// into dw/db (fp32 [cols], stored) or, where dw_dst/db_dst is non-null,
+// accumulates into that bf16 destination instead. Both repeat bit for bit
+// (the opt-in DTA_NORM_FDW panel is itself built with LDS atomics).
 struct NormBwdArgs {
   const bf16_t *dy, *ds, *x, *w;
   const float *mean, *rstd;
   bf16_t *dx, *dres;
   float *dw, *db, *pdw, *pdb;
+  bf16_t *dw_dst, *db_dst;
   int stripes;
   int64_t rows;
   int cols;  // % 8 == 0, <= DTA_NORM_BWD_MAX_COLS

@@ -18,12 +18,21 @@ DEV float gelu_f(float x) {
   float u = GELU_C * (x + GELU_A * x * x * x);
   return 0.5f * x * (1.0f + fast_tanh(u));
 }
+// 0.5 (1 + t) + 0.5 x sech^2(u) C (1 + 3A x^2). Which multiply-adds fuse is
+// spelled out, not left to the compiler: left alone it contracted this
+// expression differently from one inlining context to the next (last-bit
+// differences where the two terms cancel, x << 0), and gelu_bwd_colsum_k's
+// dx has to equal map_grad_bf16_k's bit for bit. The choices are the ones
+// map_grad_bf16_k's vector loop was compiled with until now.
 DEV float gelu_df(float x) {
+#pragma clang fp contract(off)
   float x2 = x * x;
-  float u = GELU_C * x * (1.0f + GELU_A * x2);
+  float u = (GELU_C * x) * (1.0f + GELU_A * x2);
   float t = fast_tanh(u);
-  float sech2 = 1.0f - t * t;
-  return 0.5f * (1.0f + t) + 0.5f * x * sech2 * GELU_C * (1.0f + 3.0f * GELU_A * x2);
+  float sech2 = __builtin_fmaf(-t, t, 1.0f);
+  float q = __builtin_fmaf(3.0f * GELU_A, x2, 1.0f);
+  float p = (((0.5f * x) * sech2) * GELU_C) * q;
+  return __builtin_fmaf(1.0f + t, 0.5f, p);
 }
 DEV float silu_f(float x) { return x / (1.0f + fast_exp(-x)); }
 DEV float silu_df(float x) {
@@ -256,21 +265,159 @@ __global__ void colsum_part_k(const ushort* __restrict__ x,
   for (int j = 0; j < 8; ++j) p[j] = acc[j];
 }
 
-// 2D: blockIdx.y owns a chunk of stripes (a 1-block serial loop over 1024
-// stripes measured 190 us — pure latency chain); <=32 atomics per output
-// address is noise.
-__global__ void colsum_reduce_k(const float* __restrict__ part,
-                                float* __restrict__ out, int stripes,
-                                int cols) {
-  const int c4 = (blockIdx.x * blockDim.x + threadIdx.x) * 4;
-  if (c4 >= cols) return;
-  const int s0 = (stripes * blockIdx.y) / gridDim.y;
-  const int s1 = (stripes * (blockIdx.y + 1)) / gridDim.y;
-  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-  for (int s_ = s0; s_ < s1; ++s_)
-    acc += *reinterpret_cast<const f32x4*>(part + int64_t(s_) * cols + c4);
+// any cols (no 16 B row alignment): one column per lane, panel rows padded
+// to ld = cols rounded up to 4 with the pad written as zero
+__global__ void colsum_part_any_k(const ushort* __restrict__ x,
+                                  float* __restrict__ part, int64_t rows,
+                                  int cols, int ld) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= ld) return;
+  const int64_t r0 = (rows * blockIdx.y) / gridDim.y;
+  const int64_t r1 = (rows * (blockIdx.y + 1)) / gridDim.y;
+  float acc = 0.f;
+  if (c < cols)
+    for (int64_t r = r0; r < r1; ++r) acc += bf2f(x[r * int64_t(cols) + c]);
+  part[int64_t(blockIdx.y) * ld + c] = acc;
+}
+
+// dx = bf16(dy * gelu'(x)) as map_grad_bf16_k<gelu_df> writes it, and the
+// column sums of those ROUNDED values (what colsum(dx) sums) into one row
+// of the [stripes, cols] panel: colsum_part_k's layout, so the fc bias
+// gradient costs no second pass over dx. Two rows per iteration keep two
+// 16 B loads per operand in flight, each contiguous across the wave.
+__global__ void gelu_bwd_colsum_k(const ushort* __restrict__ dy,
+                                  const ushort* __restrict__ x,
+                                  ushort* __restrict__ dx,
+                                  float* __restrict__ part, int64_t rows,
+                                  int cols) {
+  const int c8 = (blockIdx.x * blockDim.x + threadIdx.x) * 8;
+  if (c8 >= cols) return;
+  const int64_t r0 = (rows * blockIdx.y) / gridDim.y;
+  const int64_t r1 = (rows * (blockIdx.y + 1)) / gridDim.y;
+  float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  int64_t r = r0;
+  for (; r + 2 <= r1; r += 2) {
+    const int64_t ia = r * int64_t(cols) + c8, ib = ia + cols;
+    s16x8 da = *reinterpret_cast<const s16x8*>(dy + ia);
+    s16x8 db = *reinterpret_cast<const s16x8*>(dy + ib);
+    s16x8 xa = *reinterpret_cast<const s16x8*>(x + ia);
+    s16x8 xb = *reinterpret_cast<const s16x8*>(x + ib);
+    s16x8 oa, ob;
 #pragma unroll
-  for (int j = 0; j < 4; ++j) atomicAdd(out + c4 + j, acc[j]);
+    for (int j = 0; j < 8; ++j) {
+      oa[j] = f2bf(bf2f(ushort(da[j])) * gelu_df(bf2f(ushort(xa[j]))));
+      ob[j] = f2bf(bf2f(ushort(db[j])) * gelu_df(bf2f(ushort(xb[j]))));
+    }
+    *reinterpret_cast<s16x8*>(dx + ia) = oa;
+    *reinterpret_cast<s16x8*>(dx + ib) = ob;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      acc[j] += bf2f(ushort(oa[j]));
+      acc[j] += bf2f(ushort(ob[j]));
+    }
+  }
+  if (r < r1) {
+    const int64_t ia = r * int64_t(cols) + c8;
+    s16x8 da = *reinterpret_cast<const s16x8*>(dy + ia);
+    s16x8 xa = *reinterpret_cast<const s16x8*>(x + ia);
+    s16x8 oa;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      oa[j] = f2bf(bf2f(ushort(da[j])) * gelu_df(bf2f(ushort(xa[j]))));
+      acc[j] += bf2f(ushort(oa[j]));
+    }
+    *reinterpret_cast<s16x8*>(dx + ia) = oa;
+  }
+  float* p = part + int64_t(blockIdx.y) * cols + c8;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) p[j] = acc[j];
+}
+
+// Phase 2 of every column reduction (colsum, norm dγ/dβ, GELU-backward
+// bias): folds one or two [stripes, ld] fp32 panels over the stripes and
+// writes each output once — an fp32 store, or dst = bf16(float(dst) + sum),
+// the rounding accum_f32_bf16_k applies. No atomics, no pre-zeroed output,
+// a fixed summation order for a given (stripes, cols): results repeat bit
+// for bit. A block owns FIN_COLS columns; thread t takes the 4 columns of
+// lane pair t & 1 and the stripes t >> 1, t >> 1 + 128, ...; xor-shuffles
+// fold the 32 stripe lanes of a wave, LDS the 4 waves. 768 columns are 96
+// blocks with 16-deep load chains at 2048 stripes (the two earlier designs:
+// one block, a serial 1024-deep chain, 190 us; 32 y-blocks finishing with
+// atomicAdd into a zero-filled output, 15 to 31 us plus the fill).
+constexpr int FIN_THREADS = 256;
+constexpr int FIN_COLS = 8;
+constexpr int FIN_CL = FIN_COLS / 4;            // column lanes per block
+constexpr int FIN_SL = FIN_THREADS / FIN_CL;    // stripe lanes per block
+static_assert(FIN_CL == 2 && FIN_THREADS == 4 * WAVE,
+              "colred_finish_k's shuffle tree folds lanes 2..63 of 4 waves");
+
+DEV void finish_write(f32x4 v, float* out, ushort* dst, int c4, int cols) {
+  if (dst) {
+    ushort* d = dst + c4;
+    // flat-plane views are unpadded: vector access only where this
+    // thread's 4 elements are 8 B aligned
+    if (c4 + 4 <= cols && (reinterpret_cast<uintptr_t>(d) & 7) == 0) {
+      s16x4 o = *reinterpret_cast<const s16x4*>(d);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) o[j] = f2bf(bf2f(ushort(o[j])) + v[j]);
+      *reinterpret_cast<s16x4*>(d) = o;
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (c4 + j < cols) d[j] = f2bf(bf2f(d[j]) + v[j]);
+    }
+  } else if (c4 + 4 <= cols && (reinterpret_cast<uintptr_t>(out + c4) & 15) == 0) {
+    *reinterpret_cast<f32x4*>(out + c4) = v;
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (c4 + j < cols) out[c4 + j] = v[j];
+  }
+}
+
+__global__ void __launch_bounds__(FIN_THREADS)
+colred_finish_k(const float* __restrict__ p0, const float* __restrict__ p1,
+                float* __restrict__ out0, float* __restrict__ out1,
+                ushort* __restrict__ dst0, ushort* __restrict__ dst1,
+                int stripes, int cols, int ld) {
+  __shared__ f32x4 lds[2][FIN_THREADS / WAVE][FIN_CL];
+  const int cl = threadIdx.x & (FIN_CL - 1), sl = threadIdx.x / FIN_CL;
+  const int wid = threadIdx.x / WAVE;
+  const int c4 = (blockIdx.x * FIN_CL + cl) * 4;
+  const bool live = c4 < ld;   // ld % 4 == 0: the whole f32x4 is in the row
+  f32x4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = {0.f, 0.f, 0.f, 0.f};
+  if (live) {
+    const float* q0 = p0 + c4;
+    const float* q1 = p1 ? p1 + c4 : nullptr;
+#pragma unroll 4
+    for (int s_ = sl; s_ < stripes; s_ += FIN_SL) {
+      a0 += *reinterpret_cast<const f32x4*>(q0 + int64_t(s_) * ld);
+      if (q1) a1 += *reinterpret_cast<const f32x4*>(q1 + int64_t(s_) * ld);
+    }
+  }
+#pragma unroll
+  for (int off = FIN_CL; off < WAVE; off <<= 1) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      a0[j] += __shfl_xor(a0[j], off);
+      a1[j] += __shfl_xor(a1[j], off);
+    }
+  }
+  if ((threadIdx.x & (WAVE - 1)) < FIN_CL) {
+    lds[0][wid][cl] = a0;
+    lds[1][wid][cl] = a1;
+  }
+  __syncthreads();
+  if (threadIdx.x < FIN_CL && live) {
+    f32x4 r0 = lds[0][0][cl], r1 = lds[1][0][cl];
+#pragma unroll
+    for (int w = 1; w < FIN_THREADS / WAVE; ++w) {
+      r0 += lds[0][w][cl];
+      r1 += lds[1][w][cl];
+    }
+    finish_write(r0, out0, dst0, c4, cols);
+    if (p1) finish_write(r1, out1, dst1, c4, cols);
+  }
 }
 
 // -- counter-based dropout (residual/embedding paths; transformers GPT-2
@@ -380,14 +527,35 @@ void launch_l2norm_sq(const float* x, int64_t n, float* out, hipStream_t s) {
 void launch_f32_to_bf16(const float* x, bf16_t* y, int64_t n, hipStream_t s) {
   LAUNCH_EW(f32_to_bf16_k, n, x, y, n);
 }
-void launch_colsum(const bf16_t* x, float* part, float* out, int64_t rows,
-                   int cols, int stripes, hipStream_t s) {
+void launch_colred_finish(const ColFinishArgs& a, hipStream_t s) {
+  const int grid = (a.ld / 4 + FIN_CL - 1) / FIN_CL;
+  colred_finish_k<<<grid, FIN_THREADS, 0, s>>>(a.p0, a.p1, a.out0, a.out1,
+                                               a.dst0, a.dst1, a.stripes,
+                                               a.cols, a.ld);
+}
+void launch_colsum(const bf16_t* x, float* part, float* out, bf16_t* dst,
+                   int64_t rows, int cols, int stripes, hipStream_t s) {
+  const int ld = dta_colred_ld(cols);
+  if (cols % 8 == 0) {
+    const ColRedCfg cfg = dta_colred_cfg(rows, cols);
+    dim3 g1(cfg.gx, unsigned(stripes));
+    colsum_part_k<<<g1, cfg.threads, 0, s>>>(x, part, rows, cols);
+  } else {
+    dim3 g1((ld + 255) / 256, unsigned(stripes));
+    colsum_part_any_k<<<g1, 256, 0, s>>>(x, part, rows, cols, ld);
+  }
+  launch_colred_finish({part, nullptr, out, nullptr, dst, nullptr, stripes,
+                        cols, ld}, s);
+}
+void launch_gelu_bwd_colsum(const bf16_t* dy, const bf16_t* x, bf16_t* dx,
+                            float* part, float* out, bf16_t* dst,
+                            int64_t rows, int cols, int stripes,
+                            hipStream_t s) {
   const ColRedCfg cfg = dta_colred_cfg(rows, cols);
   dim3 g1(cfg.gx, unsigned(stripes));
-  colsum_part_k<<<g1, cfg.threads, 0, s>>>(x, part, rows, cols);
-  const int g2 = (cols / 4 + 255) / 256;
-  const int ry = stripes < 32 ? stripes : 32;
-  colsum_reduce_k<<<dim3(g2, ry), 256, 0, s>>>(part, out, stripes, cols);
+  gelu_bwd_colsum_k<<<g1, cfg.threads, 0, s>>>(dy, x, dx, part, rows, cols);
+  launch_colred_finish({part, nullptr, out, nullptr, dst, nullptr, stripes,
+                        cols, cols}, s);
 }
 void launch_dropout(const bf16_t* x, bf16_t* y, int64_t n,
                     const DropParams& d, hipStream_t s) {

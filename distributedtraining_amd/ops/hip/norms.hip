@@ -5,8 +5,9 @@
 // bwd: split in two streaming kernels (measured: a fused version spent
 //      ~95% of its time in a 2048-way atomicAdd flush of dγ/dβ):
 //        * dx kernel — pure streaming, no reductions across rows;
-//        * dγ/dβ kernel — column-parallel over ~256 row stripes,
-//          ≤256 atomic adds per output address (Guideline 12).
+//        * dγ/dβ kernel — column-parallel over row stripes into a partial
+//          panel, folded by launch_colred_finish (elementwise.hip): no
+//          atomics, each output written once.
 //
 // Replaces the implicit LayerNorm of the reference's GPT-2 fwd/bwd
 // (transformers internals; SURVEY.md §2.2 op table).
@@ -279,8 +280,8 @@ __global__ void norm_bwd_dx_k(const ushort* __restrict__ dy,
 // Phase 1: each (col-tile, stripe) block accumulates its stripe's rows into
 // a [stripes, cols] fp32 partial panel (vectorized s16x8 row reads) — a
 // single-phase version with ~1024 same-address atomicAdds per column
-// measured 4x slower (per-address L2 serialization). Phase 2 reduces the
-// panel 2D with <=32 atomics per output address.
+// measured 4x slower (per-address L2 serialization). Phase 2 is
+// launch_colred_finish.
 template <bool RMS>
 __global__ void norm_bwd_dwdb_part_k(const ushort* __restrict__ dy,
                                      const ushort* __restrict__ x,
@@ -314,30 +315,6 @@ __global__ void norm_bwd_dwdb_part_k(const ushort* __restrict__ dy,
     float* pb = pdb + int64_t(blockIdx.y) * cols + c8;
 #pragma unroll
     for (int j = 0; j < 8; ++j) pb[j] = db_acc[j];
-  }
-}
-
-// 2D over (col tiles, stripe chunks); <=32 atomics per output address
-// (a 1-block serial stripe loop measured 330 us — pure latency chain).
-__global__ void dwdb_reduce_k(const float* __restrict__ pdw,
-                              const float* __restrict__ pdb,
-                              float* __restrict__ dw, float* __restrict__ db,
-                              int stripes, int cols) {
-  const int c4 = (blockIdx.x * blockDim.x + threadIdx.x) * 4;
-  if (c4 >= cols) return;
-  const int s0 = (stripes * blockIdx.y) / gridDim.y;
-  const int s1 = (stripes * (blockIdx.y + 1)) / gridDim.y;
-  f32x4 aw = {0.f, 0.f, 0.f, 0.f};
-  f32x4 ab = {0.f, 0.f, 0.f, 0.f};
-  for (int s_ = s0; s_ < s1; ++s_) {
-    aw += *reinterpret_cast<const f32x4*>(pdw + int64_t(s_) * cols + c4);
-    if (pdb)
-      ab += *reinterpret_cast<const f32x4*>(pdb + int64_t(s_) * cols + c4);
-  }
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    atomicAdd(dw + c4 + j, aw[j]);
-    if (pdb) atomicAdd(db + c4 + j, ab[j]);
   }
 }
 
@@ -410,12 +387,6 @@ void launch_norm_bwd(const NormBwdArgs& a, hipStream_t s) {
               a.dy, a.x, a.mean, a.rstd, a.pdw, a.pdb, a.rows, a.cols);
     }
   }, a.rms, a.ds != nullptr, d.thr16 != 0, dta_norm_fused_dwdb(a.cols));
-  const int g3 = (a.cols / 4 + 255) / 256;
-  // stripe-parallelism scales with the panel height (the fused path
-  // produces up to 4096 panel rows; 32 y-blocks left 128-deep serial
-  // loops on an underfilled chip)
-  const int ry =
-      a.stripes < 32 ? a.stripes : (a.stripes > 1024 ? 256 : 32);
-  dwdb_reduce_k<<<dim3(g3, ry), 256, 0, s>>>(a.pdw, a.pdb, a.dw, a.db,
-                                             a.stripes, a.cols);
+  launch_colred_finish({a.pdw, a.pdb, a.dw, a.db, a.dw_dst, a.db_dst,
+                        a.stripes, a.cols, a.cols}, s);
 }
