@@ -206,6 +206,8 @@ def main(argv=None) -> int:
                 miner.base = st["base"].to(fp.device)
                 miner.step_count = int(st.get("step_count", 0))
                 miner.opt.reset_state()  # reference resume contract
+                # the LR schedule runs over the miner's lifetime
+                miner.opt.set_schedule_step(miner.step_count)
                 print(f"miner {hotkey}: resumed at step {miner.step_count}")
         else:
             miner.maybe_pull_base()
@@ -218,9 +220,14 @@ def main(argv=None) -> int:
         store.push_train_state({"flat_master": fp.master.cpu(),
                                 "base": miner.base.cpu(),
                                 "step_count": miner.step_count})
+        # guarded-step readings (None where that guard is off); the loss
+        # read right here already syncs
+        guard = {k: float(v) for k, v in (
+            ("grad_norm", miner.opt.grad_norm), ("lr", miner.opt.lr_now),
+            ("skipped_steps", miner.opt.skipped_steps)) if v is not None}
         metrics.log(miner.step_count, loss=miner.average_loss(),
                     perplexity=miner.perplexity(),
-                    staleness_s=miner.gradient_staleness())
+                    staleness_s=miner.gradient_staleness(), **guard)
         metrics.close()
         print(f"miner {hotkey}: {ns.steps} steps, "
               f"avg loss {miner.average_loss():.4f}")

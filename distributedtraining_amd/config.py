@@ -101,6 +101,41 @@ class TrainConfig:
                                      # step-based here so behavior is deterministic
     pull_interval_steps: int = 100   # reference check_update_interval 300 s
     dtype: str = "bf16"          # compute dtype; master weights stay fp32
+    # guarded optimizer step (parallel/flat.py FusedAdamW); every default is
+    # off and leaves the step what it was
+    max_grad_norm: float = 0.0   # > 0: clip the global gradient norm to this
+    skip_nonfinite: bool = False  # drop a step whose gradient is NaN/Inf
+    lr_schedule: str = "constant"  # constant | linear | cosine (after warmup)
+    warmup_steps: int = 0        # linear warmup from lr/warmup_steps to lr
+    total_steps: int = 0         # linear / cosine reach min_lr here
+    min_lr: float = 0.0
+
+    def validate(self) -> None:
+        validate_guard(self.lr, self.max_grad_norm, self.lr_schedule,
+                       self.warmup_steps, self.total_steps, self.min_lr)
+
+
+LR_SCHEDULES = ("constant", "linear", "cosine")
+
+
+def validate_guard(lr: float, max_grad_norm: float, lr_schedule: str,
+                   warmup_steps: int, total_steps: int,
+                   min_lr: float) -> None:
+    """The combinations the guarded step accepts (raises ValueError)."""
+    if lr_schedule not in LR_SCHEDULES:
+        raise ValueError(f"lr_schedule must be one of {LR_SCHEDULES}, "
+                         f"got {lr_schedule!r}")
+    if not max_grad_norm >= 0:
+        raise ValueError(f"max_grad_norm must be >= 0, got {max_grad_norm}")
+    if warmup_steps < 0:
+        raise ValueError(f"warmup_steps must be >= 0, got {warmup_steps}")
+    if lr_schedule != "constant" and not total_steps > warmup_steps:
+        raise ValueError(
+            f"lr_schedule {lr_schedule!r} needs total_steps > warmup_steps "
+            f">= 0, got total_steps={total_steps} "
+            f"warmup_steps={warmup_steps}")
+    if not min_lr <= lr:
+        raise ValueError(f"min_lr ({min_lr}) must be <= lr ({lr})")
 
 
 @dataclass
@@ -228,4 +263,5 @@ def from_args(argv=None) -> Config:
             v = getattr(ns, f"{prefix}__{f.name}", None)
             if v is not None:
                 setattr(sub, f.name, v)
+    cfg.train.validate()
     return cfg

@@ -38,6 +38,8 @@ __all__ = [
     "decode_attention", "rope", "adamw_step", "delta_sub", "axpy_",
     "weighted_merge",
     "grad_merge_weights", "has_nan", "l2norm",
+    "grad_sumsq_blocks", "grad_sumsq_partials", "step_control",
+    "adamw_step_guarded", "lr_schedule",
     "quantize_blockwise_int8", "dequantize_blockwise_int8",
     "dropout", "rng_tick",
 ]
@@ -1165,6 +1167,136 @@ def adamw_tick(t_dev: torch.Tensor, bc_dev: torch.Tensor,
 
 
 # --------------------------------------------------------------------------
+# Guarded step: gradient clipping, non-finite skip and the LR schedule with
+# no host round-trip. grad_sumsq_partials -> step_control ->
+# adamw_step_guarded talk through a device control block
+#   ctl_f fp32[6]  {lr, coef, grad_norm, bc1, bc2, unused}
+#   ctl_i int32[4] {t, sched_step, skip_now, skipped_total}
+# (hip/adamw.hip). The CPU paths keep the block in host tensors and have the
+# same semantics.
+# --------------------------------------------------------------------------
+LR_SCHEDULES = ("constant", "linear", "cosine")
+CTL_LR, CTL_COEF, CTL_NORM, CTL_BC1, CTL_BC2 = range(5)
+CTL_T, CTL_SCHED, CTL_SKIP_NOW, CTL_SKIPPED = range(4)
+
+
+def lr_schedule(schedule: str, s: int, lr_max: float, min_lr: float = 0.0,
+                warmup_steps: int = 0, total_steps: int = 0) -> float:
+    """The schedule's value at step ``s`` (counted from 1), in double: linear
+    warmup to ``lr_max``, then constant, or linear / cosine decay to
+    ``min_lr`` at ``total_steps`` and flat after it."""
+    if s <= warmup_steps:
+        return lr_max * s / warmup_steps
+    if schedule == "constant":
+        return lr_max
+    p = min(1.0, (s - warmup_steps) / max(1, total_steps - warmup_steps))
+    if schedule == "linear":
+        return lr_max + (min_lr - lr_max) * p
+    assert schedule == "cosine", schedule
+    return min_lr + 0.5 * (lr_max - min_lr) * (1.0 + math.cos(math.pi * p))
+
+
+def grad_sumsq_blocks(n: int, dtype: torch.dtype,
+                      device: torch.device) -> int:
+    """Length of the partial buffer grad_sumsq_partials fills for a plane of
+    ``n`` elements: a fixed function of n and dtype."""
+    if torch.device(device).type == "cuda":
+        return int(require_ext().grad_sumsq_blocks(
+            n, dtype == torch.bfloat16))
+    return 1
+
+
+def grad_sumsq_partials(flat: torch.Tensor, out: torch.Tensor) -> None:
+    """out[b] = partial sum of squares of ``flat`` (bf16 or fp32); the
+    partials add up to |flat|^2. Every element of ``out`` is stored, with no
+    atomics, so the values repeat bit for bit. A bf16 value whose square
+    overflows fp32 gives an infinite partial."""
+    if use_hip(flat):
+        require_ext().grad_sumsq_partials(flat, out)
+        return
+    out.zero_()
+    out[0] = flat.double().pow(2).sum().to(torch.float32)
+
+
+def step_control(partials: Optional[torch.Tensor], ctl_f: torch.Tensor,
+                 ctl_i: torch.Tensor, beta1: float, beta2: float,
+                 max_norm: float = 0.0, skip_nonfinite: bool = False,
+                 schedule: str = "constant", lr_max: float = 5e-4,
+                 min_lr: float = 0.0, warmup_steps: int = 0,
+                 total_steps: int = 0) -> None:
+    """The tick of a guarded step. Folds ``partials`` (None: no norm taken)
+    in double, then writes the control block: grad_norm, the clip factor
+    coef = min(1, max_norm / (norm + 1e-6)) (1 when max_norm <= 0), skip_now
+    = skip_nonfinite and the sum is not finite, sched_step += 1, lr =
+    lr_schedule(sched_step), and, unless skipping, t += 1 with the bias
+    corrections of t. With skip_nonfinite off a non-finite norm is not
+    special-cased: coef is whatever the formula gives, as in
+    torch.nn.utils.clip_grad_norm_."""
+    sched = LR_SCHEDULES.index(schedule)
+    if use_hip(ctl_f):
+        require_ext().step_control(
+            partials if partials is not None else ctl_f.new_empty(0), ctl_f,
+            ctl_i, beta1, beta2, max_norm, skip_nonfinite, sched, lr_max,
+            min_lr, warmup_steps, total_steps)
+        return
+    import numpy as np
+    if partials is None and (max_norm > 0 or skip_nonfinite):
+        raise ValueError("clipping and the non-finite skip need the norm "
+                         "partials")
+    total = float(partials.double().sum()) if partials is not None else 0.0
+    with np.errstate(all="ignore"):
+        norm = np.float32(np.sqrt(np.float64(total)))
+        coef = np.float32(1.0)
+        if max_norm > 0:
+            c = np.float32(max_norm) / (norm + np.float32(1e-6))
+            coef = np.float32(1.0) if c > 1.0 else c
+    skip = bool(skip_nonfinite and not math.isfinite(total))
+    s = int(ctl_i[CTL_SCHED]) + 1
+    ctl_i[CTL_SCHED] = s
+    if not skip:
+        t = int(ctl_i[CTL_T]) + 1
+        ctl_i[CTL_T] = t
+        ctl_f[CTL_BC1] = 1.0 - beta1 ** t
+        ctl_f[CTL_BC2] = 1.0 - beta2 ** t
+    ctl_f[CTL_LR] = lr_schedule(schedule, s, lr_max, min_lr, warmup_steps,
+                                total_steps)
+    ctl_f[CTL_COEF] = float(coef)
+    ctl_f[CTL_NORM] = float(norm)
+    ctl_i[CTL_SKIP_NOW] = int(skip)
+    ctl_i[CTL_SKIPPED] += int(skip)
+
+
+def adamw_step_guarded(master: torch.Tensor, grad: torch.Tensor,
+                       m: torch.Tensor, v: torch.Tensor,
+                       out_bf16: Optional[torch.Tensor], ctl_f: torch.Tensor,
+                       ctl_i: torch.Tensor, beta1: float = 0.9,
+                       beta2: float = 0.999, eps: float = 1e-8,
+                       weight_decay: float = 0.01) -> None:
+    """adamw_step with lr, the bias corrections and the clip factor read
+    from the control block step_control wrote. skip_now set: nothing is
+    touched. The clip factor scales the gradient in registers; ``grad``
+    itself is never modified."""
+    if use_hip(master):
+        require_ext().adamw_step_guarded(
+            master, grad, m, v,
+            out_bf16 if out_bf16 is not None
+            else master.new_empty(0).to(torch.bfloat16),
+            ctl_f, ctl_i, beta1, beta2, eps, weight_decay)
+        return
+    if int(ctl_i[CTL_SKIP_NOW]):
+        return
+    lr, coef, _, bc1, bc2, _ = ctl_f.tolist()
+    g = grad.float() * coef
+    master.mul_(1.0 - lr * weight_decay)
+    m.mul_(beta1).add_(g, alpha=1 - beta1)
+    v.mul_(beta2).addcmul_(g, g, value=1 - beta2)
+    denom = (v / bc2).sqrt_().add_(eps)
+    master.addcdiv_(m, denom, value=-lr / bc1)
+    if out_bf16 is not None:
+        out_bf16.copy_(master.to(out_bf16.dtype))
+
+
+# --------------------------------------------------------------------------
 # Delta / merge primitives over flat buffers
 # --------------------------------------------------------------------------
 def delta_sub(w: torch.Tensor, base: torch.Tensor,
@@ -1318,7 +1450,9 @@ def has_nan(flat: torch.Tensor) -> bool:
 
 
 def l2norm(flat: torch.Tensor) -> float:
-    """Grad-norm for clip/normalize (reference: training_manager.py:181-196)."""
+    """Norm of an fp32 plane as a host float (reference:
+    training_manager.py:181-196). Syncs; the train step's clipping takes its
+    norm with grad_sumsq_partials + step_control instead."""
     if use_hip(flat):
         return float(require_ext().l2norm_sq(flat)) ** 0.5
     return float(flat.float().pow(2).sum().item()) ** 0.5

@@ -280,6 +280,96 @@ void adamw_tick(Tensor t, Tensor bc, double beta1, double beta2) {
                     stream());
 }
 
+// ---- guarded step: norm partials -> control block -> AdamW ------------------
+// None of the three syncs or allocates; all are graph-capturable.
+bool flat_grad_is_bf16(const Tensor& g, const char* name) {
+  TORCH_CHECK(g.is_cuda(), name, " must be on GPU");
+  TORCH_CHECK(g.is_contiguous(), name, " must be contiguous");
+  const bool gb = g.scalar_type() == torch::kBFloat16;
+  TORCH_CHECK(gb || g.scalar_type() == torch::kFloat32, name,
+              " must be bf16 or fp32");
+  return gb;
+}
+void check_ctl(const Tensor& ctl_f, const Tensor& ctl_i, const Tensor& like) {
+  check_f32(ctl_f, "ctl_f");
+  TORCH_CHECK(ctl_f.numel() == 6, "ctl_f must be fp32[6]");
+  TORCH_CHECK(ctl_i.is_cuda() && ctl_i.scalar_type() == torch::kInt32 &&
+                  ctl_i.is_contiguous() && ctl_i.numel() == 4,
+              "ctl_i must be a contiguous int32[4] on GPU");
+  TORCH_CHECK(ctl_f.device() == like.device() &&
+                  ctl_i.device() == like.device(),
+              "control block must be on the device of the plane");
+}
+int64_t grad_sumsq_blocks(int64_t n, bool is_bf16) {
+  TORCH_CHECK(n >= 1, "empty plane");
+  return dta_gradnorm_blocks(n, is_bf16);
+}
+void grad_sumsq_partials(Tensor flat, Tensor out) {
+  const bool gb = flat_grad_is_bf16(flat, "flat");
+  TORCH_CHECK(flat.numel() >= 1, "empty plane");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(flat.data_ptr()) % 16 == 0,
+              "flat must be 16 B aligned");
+  check_f32(out, "out");
+  TORCH_CHECK(out.device() == flat.device(), "out must be on flat's device");
+  TORCH_CHECK(out.numel() == dta_gradnorm_blocks(flat.numel(), gb),
+              "out must have grad_sumsq_blocks(n) elements");
+  launch_gradnorm_part(flat.data_ptr(), gb, out.data_ptr<float>(),
+                       flat.numel(), stream());
+}
+// part: empty tensor => tick + schedule only
+void step_control(Tensor part, Tensor ctl_f, Tensor ctl_i, double beta1,
+                  double beta2, double max_norm, bool skip_nonfinite,
+                  int64_t schedule, double lr_max, double min_lr,
+                  int64_t warmup_steps, int64_t total_steps) {
+  check_ctl(ctl_f, ctl_i, ctl_f);
+  const bool has_part = part.numel() > 0;
+  if (has_part) {
+    check_f32(part, "part");
+    TORCH_CHECK(part.device() == ctl_f.device(),
+                "part must be on the control block's device");
+  }
+  TORCH_CHECK(has_part || (max_norm <= 0.0 && !skip_nonfinite),
+              "clipping and the non-finite skip need the norm partials");
+  TORCH_CHECK(part.numel() <= (int64_t(1) << 30), "too many partials");
+  TORCH_CHECK(schedule >= LR_CONSTANT && schedule <= LR_COSINE,
+              "unknown schedule");
+  TORCH_CHECK(warmup_steps >= 0 && warmup_steps < (int64_t(1) << 31) &&
+                  total_steps >= 0 && total_steps < (int64_t(1) << 31),
+              "warmup_steps / total_steps out of range");
+  TORCH_CHECK(schedule == LR_CONSTANT || total_steps > warmup_steps,
+              "linear / cosine need total_steps > warmup_steps");
+  launch_step_ctl({has_part ? part.data_ptr<float>() : nullptr,
+                   int(part.numel()), ctl_f.data_ptr<float>(),
+                   ctl_i.data_ptr<int>(), beta1, beta2, float(max_norm),
+                   skip_nonfinite ? 1 : 0, int(schedule), lr_max, min_lr,
+                   int(warmup_steps), int(total_steps)},
+                  stream());
+}
+void adamw_step_guarded(Tensor master, Tensor grad, Tensor m, Tensor v,
+                        Tensor out_bf16, Tensor ctl_f, Tensor ctl_i,
+                        double beta1, double beta2, double eps, double wd) {
+  check_f32(master, "master"); check_f32(m, "m"); check_f32(v, "v");
+  const bool gb = flat_grad_is_bf16(grad, "grad");
+  const int64_t n = master.numel();
+  TORCH_CHECK(grad.numel() == n && m.numel() == n && v.numel() == n,
+              "master, grad, m and v must have one length");
+  TORCH_CHECK(grad.device() == master.device() &&
+                  m.device() == master.device() &&
+                  v.device() == master.device(), "planes on one device");
+  check_ctl(ctl_f, ctl_i, master);
+  bf16_t* outp = nullptr;
+  if (out_bf16.numel()) {
+    check_bf16(out_bf16, "out_bf16");
+    TORCH_CHECK(out_bf16.numel() == n && out_bf16.device() == master.device(),
+                "out_bf16 must match master");
+    outp = bfp_mut(out_bf16);
+  }
+  launch_adamw_guarded(master.data_ptr<float>(), grad.data_ptr(), gb,
+                       m.data_ptr<float>(), v.data_ptr<float>(), outp,
+                       ctl_f.data_ptr<float>(), ctl_i.data_ptr<int>(), beta1,
+                       beta2, float(eps), float(wd), n, stream());
+}
+
 // column sum of a [rows, cols] bf16 matrix -> fp32 [cols] (bias gradient),
 // or accumulated into dst (nothing returned)
 Tensor colsum(Tensor x, OptTensor dst) {
@@ -1030,6 +1120,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("l2norm_sq", &l2norm_sq);
   m.def("adamw_step", &adamw_step);
   m.def("adamw_tick", &adamw_tick);
+  m.def("grad_sumsq_blocks", &grad_sumsq_blocks);
+  m.def("grad_sumsq_partials", &grad_sumsq_partials);
+  m.def("step_control", &step_control);
+  m.def("adamw_step_guarded", &adamw_step_guarded);
   m.def("colsum", &colsum, py::arg("x"), py::arg("dst") = py::none());
   m.def("weighted_merge", &weighted_merge);
   m.def("grad_merge_weights", &grad_merge_weights);

@@ -63,6 +63,34 @@ void launch_adamw(float* master, const void* grad, bool grad_is_bf16,
                   float eps, float wd, int64_t n, hipStream_t s);
 void launch_adamw_tick(int* t, float* bc, double beta1, double beta2,
                        hipStream_t s);
+// Guarded step (control block layout: adamw.hip header). The norm pass
+// stores dta_gradnorm_blocks(n, bf16) fp32 partials, every one of them, so
+// part needs no zero-fill; grad must be 16 B aligned.
+int dta_gradnorm_blocks(int64_t n, bool grad_is_bf16);
+void launch_gradnorm_part(const void* grad, bool grad_is_bf16, float* part,
+                          int64_t n, hipStream_t s);
+enum LrSchedule { LR_CONSTANT = 0, LR_LINEAR = 1, LR_COSINE = 2 };
+// part null (nparts 0): no norm was taken; the kernel ticks and evaluates
+// the schedule only. max_norm <= 0: no clipping. linear/cosine need
+// total_steps > warmup_steps >= 0.
+struct StepCtlArgs {
+  const float* part;
+  int nparts;
+  float* ctl_f;   // fp32[6]
+  int* ctl_i;     // int32[4]
+  double beta1, beta2;
+  float max_norm;
+  int skip_nonfinite;
+  int schedule;   // LrSchedule
+  double lr_max, min_lr;
+  int warmup_steps, total_steps;
+};
+void launch_step_ctl(const StepCtlArgs& a, hipStream_t s);
+void launch_adamw_guarded(float* master, const void* grad, bool grad_is_bf16,
+                          float* m, float* v, bf16_t* out_bf16,
+                          const float* ctl_f, const int* ctl_i, double beta1,
+                          double beta2, float eps, float wd, int64_t n,
+                          hipStream_t s);
 // Column reductions run in two phases: a producer writes a [stripes, ld]
 // fp32 partial panel, launch_colred_finish folds it over the stripes in a
 // fixed order and writes every output once. Per panel k: dstk non-null

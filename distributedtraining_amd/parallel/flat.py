@@ -27,6 +27,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops
+from ..config import validate_guard
 from ..store import DeltaCheckpoint, tensor_sha256
 
 
@@ -136,18 +137,57 @@ class FusedAdamW:
     Matches torch.optim.AdamW semantics (the reference's optimizer,
     neurons/miner.py:126) with fp32 master weights; state is deliberately
     reset on base refresh (reference design, training_manager.py:371-373).
+
+    Guarded step. Any of ``max_grad_norm > 0`` (clip the global gradient
+    norm, torch.nn.utils.clip_grad_norm_'s formula), ``skip_nonfinite``
+    (drop a step whose gradient norm is NaN/Inf; a bf16 gradient whose
+    square overflows fp32 counts as non-finite) or a schedule
+    (``lr_schedule`` constant | linear | cosine after ``warmup_steps`` of
+    linear warmup, decaying to ``min_lr`` at ``total_steps``) turns
+    ``step()`` into [norm pass if clipping or skipping] -> ops.step_control
+    -> ops.adamw_step_guarded. The three talk through a device control block
+    allocated here, so the step stays free of host syncs and replays from a
+    captured graph with a moving lr. The gradient plane is never modified.
+    With every default ``step()`` is the plain tick + AdamW it always was.
     """
 
     def __init__(self, fp: FlatParams, lr: float = 5e-4, betas=(0.9, 0.999),
-                 eps: float = 1e-8, weight_decay: float = 0.01):
+                 eps: float = 1e-8, weight_decay: float = 0.01,
+                 max_grad_norm: float = 0.0, skip_nonfinite: bool = False,
+                 lr_schedule: str = "constant", warmup_steps: int = 0,
+                 total_steps: int = 0, min_lr: float = 0.0):
+        validate_guard(lr, max_grad_norm, lr_schedule, warmup_steps,
+                       total_steps, min_lr)
         self.fp = fp
         self.lr = lr
         self.betas = betas
         self.eps = eps
         self.weight_decay = weight_decay
+        self.max_grad_norm = float(max_grad_norm)
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self.lr_schedule = lr_schedule
+        self.warmup_steps = int(warmup_steps)
+        self.total_steps = int(total_steps)
+        self.min_lr = float(min_lr)
         self.m = torch.zeros_like(fp.master)
         self.v = torch.zeros_like(fp.master)
         self.t = 0
+        # guarded step: the control block (ops.step_control) and the norm
+        # partials, allocated once so a captured graph sees fixed addresses.
+        # t then lives in ctl_i; the host self.t is not advanced.
+        self._needs_norm = self.max_grad_norm > 0 or self.skip_nonfinite
+        self.guarded = (self._needs_norm or lr_schedule != "constant"
+                        or self.warmup_steps > 0)
+        self.ctl_f = self.ctl_i = self._norm_part = None
+        if self.guarded:
+            self.ctl_f = torch.zeros(6, dtype=torch.float32,
+                                     device=fp.device)
+            self.ctl_i = torch.zeros(4, dtype=torch.int32, device=fp.device)
+            if self._needs_norm:
+                self._norm_part = torch.zeros(
+                    ops.grad_sumsq_blocks(fp.numel, fp.grad.dtype,
+                                          fp.device),
+                    dtype=torch.float32, device=fp.device)
         # device-side step counter + bias-correction buffer: the GPU step is
         # [tick kernel; adamw kernel], fully hipGraph-capturable (no host
         # state enters the kernels)
@@ -165,11 +205,56 @@ class FusedAdamW:
         if self.t_dev is not None:
             self.t_dev.zero_()
             self.bc_dev.zero_()
+        if self.guarded:
+            # t and the bias corrections only: the schedule clock and the
+            # skip count run over the miner's lifetime, not over one base
+            self.ctl_i[ops.CTL_T:ops.CTL_T + 1].zero_()
+            self.ctl_f[ops.CTL_BC1:ops.CTL_BC2 + 1].zero_()
+
+    def set_schedule_step(self, n: int) -> None:
+        """Resume: the next step() evaluates the schedule at ``n + 1``."""
+        if self.guarded:
+            self.ctl_i[ops.CTL_SCHED:ops.CTL_SCHED + 1].fill_(int(n))
+
+    # device-tensor views of the control block: reading their value is the
+    # only sync. None where the quantity does not exist (no guarded step;
+    # no norm pass).
+    @property
+    def grad_norm(self) -> Optional[torch.Tensor]:
+        """Global gradient norm of the last step (before clipping)."""
+        return self.ctl_f[ops.CTL_NORM] if self._needs_norm else None
+
+    @property
+    def lr_now(self) -> Optional[torch.Tensor]:
+        """Learning rate the last step used."""
+        return self.ctl_f[ops.CTL_LR] if self.guarded else None
+
+    @property
+    def skipped_steps(self) -> Optional[torch.Tensor]:
+        """Steps dropped for a non-finite gradient so far."""
+        return self.ctl_i[ops.CTL_SKIPPED] if self.guarded else None
+
+    def _step_guarded(self, out_bf16: Optional[torch.Tensor]) -> None:
+        if self._needs_norm:
+            ops.grad_sumsq_partials(self.fp.grad, self._norm_part)
+        ops.step_control(self._norm_part, self.ctl_f, self.ctl_i,
+                         self.betas[0], self.betas[1], self.max_grad_norm,
+                         self.skip_nonfinite, self.lr_schedule, self.lr,
+                         self.min_lr, self.warmup_steps, self.total_steps)
+        ops.adamw_step_guarded(self.fp.master, self.fp.grad, self.m, self.v,
+                               out_bf16, self.ctl_f, self.ctl_i,
+                               self.betas[0], self.betas[1], self.eps,
+                               self.weight_decay)
+        if out_bf16 is None:
+            self.fp.work.copy_(self.fp.master)
 
     @torch.no_grad()
     def step(self) -> None:
-        self.t += 1
         out_bf16 = self.fp.work if self.fp.work.dtype != torch.float32 else None
+        if self.guarded:
+            self._step_guarded(out_bf16)
+            return
+        self.t += 1
         if self.t_dev is not None:
             ops.adamw_tick(self.t_dev, self.bc_dev, self.betas[0],
                            self.betas[1])

@@ -46,7 +46,13 @@ class DeltaLoop:
         self.hotkey = hotkey
         self.on_push = on_push
         self.opt = FusedAdamW(fp, lr=cfg.lr, betas=tuple(cfg.betas),
-                              eps=cfg.eps, weight_decay=cfg.weight_decay)
+                              eps=cfg.eps, weight_decay=cfg.weight_decay,
+                              max_grad_norm=cfg.max_grad_norm,
+                              skip_nonfinite=cfg.skip_nonfinite,
+                              lr_schedule=cfg.lr_schedule,
+                              warmup_steps=cfg.warmup_steps,
+                              total_steps=cfg.total_steps,
+                              min_lr=cfg.min_lr)
         self.step_count = 0
         self._loss_acc = None   # device-resident Σ(loss·batch)
         self.total_examples = 0
