@@ -419,25 +419,75 @@ std::vector<Tensor> gelu_bwd_colsum(Tensor dy, Tensor x, OptTensor db_dst,
 }
 
 // ---- merge plane -----------------------------------------------------------
+// What every merge entry point, fp32 or packed, requires of its tables
+// before anything is launched. offsets: an integer [n_segs + 1] table; the
+// kernels read int64, so an int32 table is converted, never reinterpreted.
+int merge_n_models(int64_t n) {
+  TORCH_CHECK(n >= 1 && n <= DTA_MERGE_MAX_MODELS,
+              "merge: 1 <= n_models <= ", DTA_MERGE_MAX_MODELS);
+  return int(n);
+}
+int merge_n_segs(const Tensor& offsets) {
+  TORCH_CHECK(offsets.dim() == 1 && offsets.numel() >= 2 &&
+                  (offsets.scalar_type() == torch::kInt64 ||
+                   offsets.scalar_type() == torch::kInt32),
+              "offsets must be an int64 or int32 [n_segs + 1] tensor");
+  TORCH_CHECK(offsets.numel() <= int64_t(DTA_MERGE_LDS_LIMIT / 8),
+              "offsets do not fit the LDS budget of ", DTA_MERGE_LDS_LIMIT,
+              " B");
+  return int(offsets.numel() - 1);
+}
+Tensor merge_offsets(const Tensor& offsets, const Tensor& base) {
+  return offsets.to(base.device(), torch::kInt64).contiguous();
+}
+// W [n_models, n_segs] as fp32 on base's device; it and the offsets must fit
+// the dynamic LDS weighted_merge_k caches them in
+Tensor merge_weights(const Tensor& W, const Tensor& base, int n_models,
+                     int n_segs) {
+  TORCH_CHECK(W.dim() == 2 && W.size(0) == n_models && W.size(1) == n_segs,
+              "W must be [n_models, n_segs]");
+  TORCH_CHECK(dta_merge_shmem(n_models, n_segs) <= DTA_MERGE_LDS_LIMIT,
+              "offsets + W ([", n_models, ", ", n_segs,
+              "]) do not fit the LDS budget of ", DTA_MERGE_LDS_LIMIT, " B");
+  return W.to(base.device(), torch::kFloat32).contiguous();
+}
+// an fp32 plane of P elements. The fp32 kernels read one element per lane,
+// so unlike the packed ones (check_plane) they ask for no 16-byte alignment
+void check_plane_f32(const Tensor& t, int64_t P, const char* name) {
+  check_f32(t, name);
+  TORCH_CHECK(t.numel() == P, name, " must have P elements");
+}
+int check_deltas_f32(const Tensor& deltas, int64_t P) {
+  check_f32(deltas, "deltas");
+  TORCH_CHECK(P >= 1 && deltas.dim() == 2 && deltas.size(1) == P,
+              "deltas must be [N, P]");
+  return merge_n_models(deltas.size(0));
+}
+
 void weighted_merge(Tensor base, Tensor deltas, Tensor W, Tensor offsets,
                     Tensor out) {
-  check_f32(base, "base"); check_f32(deltas, "deltas"); check_f32(out, "out");
-  auto Wc = W.to(base.device(), torch::kFloat32).contiguous();
-  auto offs = offsets.to(base.device()).contiguous();
-  const int n_models = int(deltas.size(0));
-  const int n_segs = int(offsets.numel() - 1);
+  const int64_t P = base.numel();
+  check_plane_f32(base, P, "base"); check_plane_f32(out, P, "out");
+  const int n_models = check_deltas_f32(deltas, P);
+  const int n_segs = merge_n_segs(offsets);
+  auto Wc = merge_weights(W, base, n_models, n_segs);
+  auto offs = merge_offsets(offsets, base);
   launch_weighted_merge(base.data_ptr<float>(), deltas.data_ptr<float>(),
                         Wc.data_ptr<float>(), offs.data_ptr<int64_t>(),
-                        n_models, n_segs, base.numel(),
-                        out.data_ptr<float>(), stream());
+                        n_models, n_segs, P, out.data_ptr<float>(), stream());
 }
 
 // boundary-aligned chunk table for grad_W: [n_chunks, 3] int64 rows
 // (start, end, seg) on base's device, none crossing a segment, <= 1M
-// elements each
+// elements each. The offsets must tile [0, P): the kernel reads every
+// element between a chunk's start and end.
 Tensor grad_w_chunks(const Tensor& offsets, const Tensor& base, int n_segs) {
-  auto offs_cpu = offsets.to(torch::kCPU).contiguous();
+  auto offs_cpu = offsets.to(torch::kCPU, torch::kInt64).contiguous();
   const int64_t* op = offs_cpu.data_ptr<int64_t>();
+  TORCH_CHECK(op[0] == 0 && op[n_segs] == base.numel(),
+              "offsets must run from 0 to P");
+  for (int j = 0; j < n_segs; ++j)
+    TORCH_CHECK(op[j] <= op[j + 1], "offsets must not decrease");
   std::vector<int64_t> chunks;
   constexpr int64_t CH = 1 << 20;
   for (int j = 0; j < n_segs; ++j)
@@ -452,17 +502,26 @@ Tensor grad_w_chunks(const Tensor& offsets, const Tensor& base, int n_segs) {
       .to(base.device());
 }
 
+// g: the bf16 or fp32 [P] gradient plane both grad_W entry points read
+bool check_grad_plane(const Tensor& g, int64_t P) {
+  const bool gb = g.scalar_type() == torch::kBFloat16;
+  TORCH_CHECK(g.is_cuda() && g.is_contiguous() && g.numel() == P &&
+                  (gb || g.scalar_type() == torch::kFloat32),
+              "g must be a contiguous bf16/fp32 [P] GPU tensor");
+  return gb;
+}
+
 Tensor grad_merge_weights(Tensor g, Tensor base, Tensor deltas, Tensor merged,
                           Tensor offsets) {
-  check_f32(base, "base"); check_f32(deltas, "deltas");
-  const int n_models = int(deltas.size(0));
-  const int n_segs = int(offsets.numel() - 1);
   const int64_t P = base.numel();
+  check_plane_f32(base, P, "base"); check_plane_f32(merged, P, "merged");
+  const bool gb = check_grad_plane(g, P);
+  const int n_models = check_deltas_f32(deltas, P);
+  const int n_segs = merge_n_segs(offsets);
   auto ch = grad_w_chunks(offsets, base, n_segs);
   const int n_chunks = int(ch.numel() / 3);
   auto gw = torch::zeros({n_models, n_segs},
                          base.options().dtype(torch::kFloat32));
-  const bool gb = g.scalar_type() == torch::kBFloat16;
   launch_grad_merge_weights(g.data_ptr(), gb, base.data_ptr<float>(),
                             deltas.data_ptr<float>(),
                             merged.data_ptr<float>(),
@@ -520,15 +579,10 @@ void weighted_merge_packed(Tensor base, Tensor data, Tensor scales,
   const int64_t P = base.numel();
   check_plane(base, P, "base"); check_plane(out, P, "out");
   const PackedView d = packed_view(data, scales, P, block);
-  const int n_models = int(data.size(0));
-  const int n_segs = int(offsets.numel() - 1);
-  TORCH_CHECK(n_segs >= 1 && W.dim() == 2 && W.size(0) == n_models &&
-                  W.size(1) == n_segs, "W must be [n_models, n_segs]");
-  TORCH_CHECK(dta_merge_shmem(n_models, n_segs) <= DTA_MERGE_LDS_LIMIT,
-              "offsets + W ([", n_models, ", ", n_segs,
-              "]) do not fit the LDS budget of ", DTA_MERGE_LDS_LIMIT, " B");
-  auto Wc = W.to(base.device(), torch::kFloat32).contiguous();
-  auto offs = offsets.to(base.device(), torch::kInt64).contiguous();
+  const int n_models = merge_n_models(data.size(0));
+  const int n_segs = merge_n_segs(offsets);
+  auto Wc = merge_weights(W, base, n_models, n_segs);
+  auto offs = merge_offsets(offsets, base);
   launch_weighted_merge_packed(base.data_ptr<float>(), d,
                                Wc.data_ptr<float>(),
                                offs.data_ptr<int64_t>(), n_models, n_segs, P,
@@ -540,15 +594,11 @@ Tensor grad_merge_weights_packed(Tensor g, Tensor base, Tensor data,
                                  Tensor offsets) {
   const int64_t P = base.numel();
   check_plane(base, P, "base"); check_plane(merged, P, "merged");
-  const bool gb = g.scalar_type() == torch::kBFloat16;
-  TORCH_CHECK(g.is_cuda() && g.is_contiguous() && g.numel() == P &&
-                  (gb || g.scalar_type() == torch::kFloat32) && aligned16(g),
-              "g must be a contiguous 16-byte aligned bf16/fp32 [P] GPU "
-              "tensor");
+  const bool gb = check_grad_plane(g, P);
+  TORCH_CHECK(aligned16(g), "g must be 16-byte aligned");
   const PackedView d = packed_view(data, scales, P, block);
-  const int n_models = int(data.size(0));
-  const int n_segs = int(offsets.numel() - 1);
-  TORCH_CHECK(n_segs >= 1, "offsets must be [n_segs + 1]");
+  const int n_models = merge_n_models(data.size(0));
+  const int n_segs = merge_n_segs(offsets);
   auto ch = grad_w_chunks(offsets, base, n_segs);
   const int n_chunks = int(ch.numel() / 3);
   auto gw = torch::zeros({n_models, n_segs},
@@ -793,6 +843,23 @@ void kv_append(Tensor kn, Tensor vn, Tensor kc, Tensor vc, Tensor pos) {
   TORCH_CHECK(vn.stride(0) == kn.stride(0) && vn.stride(2) == 1,
               "vn must share kn's layout (one qkv projection)");
   TORCH_CHECK(pos.scalar_type() == torch::kInt32 && pos.is_cuda(), "pos");
+  TORCH_CHECK(kn.is_cuda() && vn.is_cuda() &&
+                  kn.scalar_type() == torch::kBFloat16 &&
+                  vn.scalar_type() == torch::kBFloat16,
+              "kn, vn must be bf16 GPU tensors");
+  // the kernel addresses row *pos of head h at h * stride(1) + pos * D
+  TORCH_CHECK(kc.is_cuda() && vc.is_cuda() &&
+                  kc.scalar_type() == torch::kBFloat16 &&
+                  vc.scalar_type() == torch::kBFloat16,
+              "kc, vc must be bf16 GPU caches");
+  TORCH_CHECK(kc.dim() == 4 && kc.stride(3) == 1 &&
+                  kc.stride(2) == kc.size(3),
+              "kc must be [B,Hk,Lmax,D] with contiguous [Lmax,D] planes");
+  TORCH_CHECK(vc.sizes() == kc.sizes() && vc.strides() == kc.strides(),
+              "vc must have kc's shape and strides");
+  TORCH_CHECK(kn.size(0) == kc.size(0) && vn.sizes() == kn.sizes() &&
+                  kn.size(2) == kc.size(1) * kc.size(3),
+              "kn, vn must be [B,1,Hk*D] of the caches' B, Hk, D");
   const int B = int(kc.size(0)), Hk = int(kc.size(1)), D = int(kc.size(3));
   launch_kv_append(bfp(kn), bfp(vn), kn.stride(0), bfp_mut(kc), bfp_mut(vc),
                    pos.data_ptr<int>(), B, Hk, D, kc.stride(0),

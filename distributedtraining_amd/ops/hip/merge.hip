@@ -5,6 +5,7 @@
 //   merged[e]  = sum_i W[i, seg(e)] * (base[e] + delta_i[e])   (:422-470)
 //   grad_W[i,j]= sum_{e in seg j} g[e] * (base[e]+delta_i[e]-merged[e])
 //                                                              (:512-522)
+//                formed as (base[e] - merged[e]) + delta_i[e], see grad_w_k
 // The reference re-loads every miner model from disk per batch; here all
 // deltas are HBM-resident and each pass streams them once. They stay in the
 // form they were gathered in: [N, P] fp32, [N, P] bf16, or blockwise int8
@@ -203,7 +204,11 @@ __global__ void grad_w_k(const void* __restrict__ gp,
                      : reinterpret_cast<const float*>(gp)[e];
     float d[1];
     delta_at<KIND, 1, WORD>(deltas, i, e, d);
-    acc = fmaf(g, base[e] + d[0] - merged[e], acc);
+    // (base - merged) first: with W near 1/N merged is base + mean delta, so
+    // that difference is exact and the sum rounds at an ulp of delta.
+    // (base + d) - merged rounds at an ulp of BASE, 6e-8 |base| / |delta|
+    // of the term (measured: docs/test_accuracy.md).
+    acc = fmaf(g, (base[e] - merged[e]) + d[0], acc);
   }
   acc = block_sum<16>(acc, lds);
   if (threadIdx.x == 0) atomicAdd(grad_w + int64_t(i) * n_segs + seg, acc);

@@ -53,6 +53,25 @@ GELU / SwiGLU (hip/elementwise.hip): the whole map is evaluated in fp32 and
 RoPE (hip/rope.hip), embedding forward (hip/embedding.hip): fp32 arithmetic,
   outputs rounded once. Embedding dwte/dwpe are fp32 sums.
 AdamW (hip/adamw.hip): master/m/v fp32; the working copy is bf16(master).
+serving GEMV (hip/gemv.hip): fp32 fmaf accumulators over the whole K (the
+  chunks of the x panel share them), fp32 wave and block fold, bias added in
+  fp32, ONE bf16 rounding at the store (gemv_k, emit): ``rounded`` is
+  bf16(exact).
+weighted_merge (hip/merge.hip): fp32 throughout, base + d rounded, then an
+  fmaf per model; the fp32 baseline is the CPU path of ops.weighted_merge.
+grad_W (hip/merge.hip, grad_w_k): terms g * ((base - merged) + d) in fp32;
+  lane t of 256 sums elements start + t, + 256, ... of a chunk of <= 2^20
+  serially in fp32, the 256 partials and then the chunks of a segment are
+  folded in fp32 (atomicAdd). The fp32 baseline (``lane_sum32``) sums in
+  exactly that order: a serial sum of 2e5 terms costs 6e-6 to 8e-6 on its
+  own and would hide the order of the two adds inside the term.
+ce_chunk + ce_finalize (hip/ce.hip): the running (m, s) of a row is fp32 in
+  exp2 units, rescaled once per tile; lse and loss_sum are the fp32
+  quantities of ce_fwd and use its references; the target logit is the bf16
+  input converted to fp32, exact.
+kv_append, delta_sub: no rounding of their own (a copy; one fp32 subtract).
+accum_f32_into_bf16: bf16(dst + src) with the sum in fp32, one rounding;
+  ``rounded`` is bf16 of the fp64 sum.
 """
 
 from __future__ import annotations
@@ -955,3 +974,426 @@ def head_loss_case():
     a = (d(x), d(w), tg, -100)
     return dict(x=x, w=w, tg=tg, exact=head_loss(*a, mode="exact"),
                 rounded=head_loss(*a, mode="rounded"))
+
+
+# ---------------------------------------------------------------------------
+# Serving GEMV
+# ---------------------------------------------------------------------------
+def gemv_kc(M: int) -> int:
+    """K chunk of the staged x panel: 8192 / MT, MT = 1, 2 or 4 rows."""
+    return 8192 // (1 if M == 1 else 2 if M == 2 else 4)
+
+
+def gemv(x, w, bias, mode="exact", mut: Optional[dict] = None):
+    """x [M,K], w [N,K], bias [N] or None (fp64). y [M,N] = x w^T + bias.
+    Mutants: drop_last_chunk (the last K chunk of gemv_kc(M) elements),
+    drop_last8, no_bias, bf16_between_chunks (the accumulator rounded to bf16
+    at every chunk boundary), row_shift (row m reads x row m - 1),
+    skip_last_col (column N - 1 left at zero)."""
+    mut = mut or {}
+    M, K = x.shape
+    kc = gemv_kc(M)
+    xs = x.roll(1, 0) if mut.get("row_shift") else x
+    hi = K
+    if mut.get("drop_last_chunk"):
+        hi = ((K - 1) // kc) * kc
+    if mut.get("drop_last8"):
+        hi = K - 8
+    if mut.get("bf16_between_chunks"):
+        acc = torch.zeros(M, w.shape[0], dtype=F64)
+        for k0 in range(0, K, kc):
+            if k0:
+                acc = bf16(acc)
+            acc = acc + xs[:, k0:k0 + kc] @ w[:, k0:k0 + kc].t()
+    else:
+        acc = xs[:, :hi] @ w[:, :hi].t()
+    if bias is not None and not mut.get("no_bias"):
+        acc = acc + bias
+    if mut.get("skip_last_col"):
+        acc = acc.clone()
+        acc[:, -1] = 0.0
+    return _rnd(mode)(acc)
+
+
+def gemv_inputs(M, N, K, bias, regime, seed=900):
+    """x [M,K], w [N,K], bias [N] or None as CPU bf16. randn: x = 0.5 randn,
+    w = 0.05 randn. cancel: row m of x is (1 + m/4) x0 and w[n] = a_n s_k x0,
+    s_k = +1 on the first half of K and -0.98 S+/S- on the second, so the two
+    halves of every dot product are 50 x the result with opposite signs.
+    bias: none | bf16 (randn, as the serving models') | x100 (100 x the rms
+    of the product)."""
+    x = randn_bf16(M, K, seed=seed, scale=0.5)
+    w = randn_bf16(N, K, seed=seed + 1, scale=0.05)
+    if regime == "cancel":
+        x0 = x[0].to(F64)
+        h = K // 2
+        s = torch.ones(K, dtype=F64)
+        s[h:] = -0.98 * float((x0[:h] ** 2).sum() / (x0[h:] ** 2).sum())
+        a = 0.05 * (1.0 + 0.1 * torch.arange(N, dtype=F64)) \
+            * (1.0 - 2.0 * (torch.arange(N) % 2))
+        x = (x0[None] * (1.0 + 0.25 * torch.arange(M, dtype=F64))[:, None]
+             ).to(torch.float32).to(torch.bfloat16)
+        w = (a[:, None] * (s * x0)[None]).to(torch.float32).to(torch.bfloat16)
+    else:
+        assert regime == "randn", regime
+    b = None
+    if bias != "none":
+        sc = {"bf16": 1.0, "x100": 100.0 * 0.025 * math.sqrt(K)}[bias]
+        b = randn_bf16(N, seed=seed + 2, scale=sc)
+    return x, w, b
+
+
+# KC = 8192 / MT and a sweep of the 256 lanes covers 2048 elements: one
+# sweep, one sweep + a vector, one chunk, one chunk + a vector, the Llama
+# down projection (M = 1); the same around KC = 4096 (M = 2) and 2048 (M = 3
+# runs the MT = 4 kernel with a padded row)
+GEMV_K = {1: (8, 2048, 2056, 8192, 8200, 14336), 2: (4096, 4104),
+          3: (2048, 2056, 4104), 4: (2048, 2056, 4104)}
+# (M, N, K, bias, regime)
+GEMV_CASES = [(M, N, K, b, "randn") for M, Ks in GEMV_K.items() for K in Ks
+              for N in (1, 5) for b in ("none", "bf16")] \
+    + [(1, 2051, 64, "bf16", "randn"), (4, 2051, 64, "bf16", "randn"),
+       (1, 5, 2048, "x100", "randn"), (4, 5, 4104, "x100", "randn"),
+       (1, 5, 14336, "none", "cancel"), (2, 5, 4104, "none", "cancel"),
+       (4, 5, 4104, "none", "cancel"), (3, 5, 2056, "none", "cancel")]
+
+
+@functools.lru_cache(maxsize=None)
+def gemv_case(case):
+    x, w, b = gemv_inputs(*case)
+    a = (d(x), d(w), None if b is None else d(b))
+    return dict(x=x, w=w, b=b, args=a, exact=gemv(*a, mode="exact"),
+                rounded=gemv(*a, mode="rounded"))
+
+
+# ---------------------------------------------------------------------------
+# Merge plane: weighted_merge and grad_W on fp32 deltas
+# ---------------------------------------------------------------------------
+def seg_ids(offsets, P):
+    return torch.repeat_interleave(torch.arange(len(offsets) - 1),
+                                   offsets[1:] - offsets[:-1],
+                                   output_size=P)
+
+
+def weighted_merge(base, deltas, W, offsets, mode="exact",
+                   mut: Optional[dict] = None):
+    """merged[e] = sum_i W[i, seg(e)] (base[e] + deltas[i, e]); base [P],
+    deltas [N,P], W [N,S] fp64 (fp32 values), offsets int64 [S+1].
+    Mutants: boundary_prev_weight (the first element of segment j > 0 takes
+    segment j - 1's weight), drop_last_model, w_transposed (W read as
+    [seg, i]), base_once (base added once, not once per model)."""
+    mut = mut or {}
+    N, P = deltas.shape
+    S = W.shape[1]
+    if mode == "rounded":
+        from distributedtraining_amd import ops
+        return ops.weighted_merge(base.float(), deltas.float(), W.float(),
+                                  offsets).to(F64)
+    seg = seg_ids(offsets, P)
+    if mut.get("boundary_prev_weight"):
+        seg = seg.clone()
+        first = offsets[1:-1][offsets[1:-1] < offsets[2:]]
+        seg[first] = seg[first - 1]
+    if mut.get("w_transposed"):
+        W = W.reshape(-1).view(S, N).t()
+    n = N - 1 if mut.get("drop_last_model") else N
+    Ws = W[:n][:, seg]
+    if mut.get("base_once"):
+        return base + (Ws * deltas[:n]).sum(0)
+    return (Ws * (base[None] + deltas[:n])).sum(0)
+
+
+GW_LANES, GW_CHUNK = 256, 1 << 20
+
+
+def lane_sum32(t: np.ndarray) -> np.float32:
+    """fp32 sum of a chunk in grad_w_k's order: lane l of 256 adds elements
+    l, l + 256, ... one at a time, then the 256 partials are folded one at a
+    time (numpy keeps the running sums in fp32, see _serial_sum32)."""
+    t = np.asarray(t, dtype=np.float32)
+    if t.size == 0:
+        return np.float32(0.0)
+    pad = (-t.size) % GW_LANES
+    a = np.concatenate([t, np.zeros(pad, np.float32)]).reshape(-1, GW_LANES)
+    part = np.cumsum(a, axis=0, dtype=np.float32)[-1]
+    return np.cumsum(part, dtype=np.float32)[-1]
+
+
+def grad_w_fp32(g, base, deltas, merged, offsets, order="cpu"):
+    """[N,S] fp32 grad_W from fp32 numpy planes, chunked and summed as the
+    kernel does. order: cpu = g ((base - merged) + d), the CPU path's and
+    the kernel's; parent = g ((base + d) - merged), the kernel's before."""
+    N = deltas.shape[0]
+    off = [int(o) for o in offsets]
+    out = np.zeros((N, len(off) - 1), np.float32)
+    bm = base - merged
+    for i in range(N):
+        t = g * ((bm + deltas[i]) if order == "cpu"
+                 else ((base + deltas[i]) - merged))
+        for j in range(len(off) - 1):
+            acc = np.float32(0.0)
+            for s0 in range(off[j], off[j + 1], GW_CHUNK):
+                acc = np.float32(
+                    acc + lane_sum32(t[s0:min(s0 + GW_CHUNK, off[j + 1])]))
+            out[i, j] = acc
+    return out
+
+
+def grad_merge_weights(g, base, deltas, merged, offsets, mode="exact",
+                       mut: Optional[dict] = None):
+    """grad_W[i,j] = sum_{e in seg j} g[e] (base[e] + deltas[i,e] -
+    merged[e]) on fp64 tensors holding the values the kernel reads.
+    Mutants: no_merged, drop_seg_last (the last element of every segment),
+    next_seg (a chunk's sum credited to segment j + 1)."""
+    mut = mut or {}
+    N, P = deltas.shape
+    S = len(offsets) - 1
+    if mode == "rounded":
+        f = lambda t: t.to(torch.float32).numpy()   # noqa: E731
+        return torch.from_numpy(grad_w_fp32(
+            f(g), f(base), f(deltas), f(merged), offsets)).to(F64)
+    seg = seg_ids(offsets, P)
+    keep = torch.ones(P, dtype=F64)
+    if mut.get("drop_seg_last"):
+        last = offsets[1:][offsets[1:] > offsets[:-1]] - 1
+        keep[last] = 0.0
+    mg = torch.zeros_like(merged) if mut.get("no_merged") else merged
+    out = torch.zeros(N, S, dtype=F64)
+    for i in range(N):
+        out[i].index_add_(0, seg, keep * g * (base + deltas[i] - mg))
+    if mut.get("next_seg"):
+        out = out.roll(1, 1)
+    return out
+
+
+def _odd_sizes(n):
+    return tuple(1 + (7 * j * j + 3 * j) % 97 for j in range(n))
+
+
+# segment tables: boundaries inside 16 B vectors; one-element segments; an
+# empty segment (two equal offsets); a single segment; 291 segments of mixed
+# odd sizes (the tensor count of Llama-3-8B); big: three chunks in one
+# segment, so one output receives three atomic adds (grad_W only)
+MERGE_TABLES = {"four": (1000, 37, 4096, 123), "ones": (1, 1, 1, 5),
+                "empty": (300, 0, 41, 7), "single": (4099,),
+                "t291": _odd_sizes(291),
+                "big": (37, 2 * GW_CHUNK + 5, 123)}
+MERGE_W = ("uniform", "rand", "signed")
+# (table, N, W kind); "loop" is built from MAX_RESIDENT_BLOCKS by the caller
+MERGE_CASES = [(t, n, wk) for t in ("four", "ones", "empty", "single", "t291")
+               for n in (1, 3, 32) for wk in MERGE_W]
+
+
+def max_resident_blocks() -> int:
+    """MAX_RESIDENT_BLOCKS, the cap of the elementwise grids, from the
+    header."""
+    import re
+    path = os.path.join(os.path.dirname(os.path.dirname(
+        os.path.abspath(__file__))), "distributedtraining_amd", "ops", "hip",
+        "dta_common.h")
+    with open(path) as f:
+        return int(re.search(r"MAX_RESIDENT_BLOCKS\s*=\s*(\d+)",
+                             f.read()).group(1))
+
+
+def merge_loop_table(max_resident_blocks: int):
+    """A plane past MAX_RESIDENT_BLOCKS x 256 elements: the capped grid of
+    weighted_merge_k (one element per lane) goes round a second time."""
+    return (max_resident_blocks * 256 - 40, 37, 4099 + 3)
+
+
+def merge_inputs(table, N, wkind, dscale=1e-3, seed=1000):
+    """base [P] randn, deltas [N,P] = dscale randn, g [P] randn (fp32), W
+    [N,S]: uniform = 1/N (the averager's start); rand in [0, 1]; signed =
+    randn shifted so that every column sums to 1 (N = 1: ones)."""
+    gen = torch.Generator().manual_seed(seed + N)
+    P, S = sum(table), len(table)
+    base = torch.randn(P, generator=gen)
+    deltas = torch.randn(N, P, generator=gen) * dscale
+    grad = torch.randn(P, generator=gen)
+    if wkind == "uniform":
+        W = torch.full((N, S), 1.0 / N)
+    elif wkind == "rand":
+        W = torch.rand(N, S, generator=gen)
+    else:
+        assert wkind == "signed", wkind
+        r = torch.randn(N, S, generator=gen)
+        W = r - r.mean(0, keepdim=True) + 1.0 / N
+    offsets = torch.tensor([0] + list(np.cumsum(table)), dtype=torch.int64)
+    return dict(P=P, base=base, deltas=deltas, W=W, g=grad, offsets=offsets)
+
+
+def merge_case_uncached(table, N, wkind):
+    t = merge_inputs(table, N, wkind)
+    a = (d(t["base"]), d(t["deltas"]), d(t["W"]), t["offsets"])
+    t.update(args=a, exact=weighted_merge(*a, mode="exact"),
+             rounded=weighted_merge(*a, mode="rounded"))
+    return t
+
+
+@functools.lru_cache(maxsize=None)
+def merge_case(case):
+    table, N, wkind = case
+    return merge_case_uncached(MERGE_TABLES[table], N, wkind)
+
+
+# grad_W: (table, N, regime, g dtype). d1e-3 / d1e-5: deltas of that scale
+# under W = 1/N, where merged = base + mean delta and the term cancels (the
+# production regime); wrand: W rand, columns not summing to 1, no
+# cancellation. The 2^21-element table keeps to three cases.
+GRADW_REGIMES = {"d1e-3": (1e-3, "uniform"), "d1e-5": (1e-5, "uniform"),
+                 "wrand": (1e-3, "rand")}
+GRADW_CASES = [(t, 3, r, gd) for t in ("four", "ones", "empty", "single",
+                                       "t291")
+               for r in GRADW_REGIMES for gd in ("fp32", "bf16")] \
+    + [("four", 32, r, "fp32") for r in GRADW_REGIMES] \
+    + [("big", 3, "d1e-5", "fp32"), ("big", 3, "d1e-5", "bf16"),
+       ("big", 3, "wrand", "fp32")]
+
+
+def gradw_case_uncached(case):
+    """merged is the fp64 merge rounded to fp32: an input that does not come
+    from the kernel under test. g_src: the fp32 plane a bf16 g was rounded
+    from."""
+    table, N, regime, gd = case
+    dscale, wkind = GRADW_REGIMES[regime]
+    t = merge_inputs(MERGE_TABLES[table], N, wkind, dscale)
+    merged = weighted_merge(d(t["base"]), d(t["deltas"]), d(t["W"]),
+                            t["offsets"]).to(torch.float32)
+    g = t["g"] if gd == "fp32" else t["g"].to(torch.bfloat16)
+    a = (d(g), d(t["base"]), d(t["deltas"]), d(merged), t["offsets"])
+    t.update(merged=merged, g_in=g, g_src=t["g"], args=a,
+             exact=grad_merge_weights(*a, mode="exact"),
+             rounded=grad_merge_weights(*a, mode="rounded"))
+    return t
+
+
+@functools.lru_cache(maxsize=None)
+def gradw_case(case):
+    return gradw_case_uncached(case)
+
+
+# ---------------------------------------------------------------------------
+# ce_chunk + ce_finalize: the logits of a CE case consumed in column tiles
+# ---------------------------------------------------------------------------
+def ce_tiles(logits, targets, tiles, ignore_index,
+             mut: Optional[dict] = None):
+    """fp64 model of ce_chunk over the column tiles (widths ``tiles``)
+    followed by ce_finalize, from the state m = -inf, s = 0, tlogit = 0.
+    Returns lse, loss_sum, count, tlogit. Mutants: no_rescale (a tile is
+    added without rescaling the running sum), v0_off (v0 off by one in the
+    target lookup), drop_tail (the scalar tail of a tile whose width is no
+    multiple of 8), count_ignored."""
+    mut = mut or {}
+    T = logits.shape[0]
+    m = torch.full((T,), float("-inf"), dtype=F64)
+    s = torch.zeros(T, dtype=F64)
+    tl = torch.zeros(T, dtype=F64)
+    ninf = torch.full((T,), float("-inf"), dtype=F64)
+    v0 = 0
+    for wd in tiles:
+        x = logits[:, v0:v0 + wd]
+        if mut.get("drop_tail"):
+            x = x[:, :wd - wd % 8]
+        M = x.amax(1) if x.shape[1] else ninf
+        mn = torch.maximum(m, M)
+        fin = torch.isfinite(mn)
+        safe = torch.where(fin, mn, torch.zeros_like(mn))
+        S = torch.exp(x - safe[:, None]).sum(1)      # = S_tile exp(M - mn)
+        keep = torch.ones_like(s) if mut.get("no_rescale") \
+            else torch.exp(m - safe)
+        s = torch.where(fin, s * keep + S, s)
+        m = mn
+        tc = targets - v0 - (1 if mut.get("v0_off") else 0)
+        hit = (tc >= 0) & (tc < wd)
+        tl[hit] = logits[hit, (v0 + tc)[hit]]
+        v0 += wd
+    assert v0 == logits.shape[1]
+    lse = m + torch.log(s)
+    valid = torch.ones(T, dtype=torch.bool) if mut.get("count_ignored") \
+        else targets != ignore_index
+    return dict(lse=lse, loss_sum=(lse - tl)[valid].sum(),
+                count=int(valid.sum()), tlogit=tl)
+
+
+# the CE shapes split into column tiles: odd widths (3 + 4; 505), a tail of
+# fewer than 8 columns, v0 no multiple of 8 (8 + 505), one tile, the GPT-2
+# vocabulary with its odd last tile, and 4099 rows (the 4096-block grid of
+# ce_chunk_k loops)
+CE_TILINGS = [((5, 7), (3, 4)), ((33, 1000), (640, 360)),
+              ((33, 1000), (1000,)), ((16, 520), (8, 505, 7)),
+              ((8, 50257), (16384, 16384, 50257 - 2 * 16384)),
+              ((4099, 24), (9, 15))]
+# (rows, vocab, regime, tiles, peak); peak first / last: one column of the
+# first / last tile raised by 12 in every row, so the row maximum arrives
+# with the first tile and never moves, or moves in the last
+CE_TILE_CASES = [(r, v, g, t, None) for (r, v), t in CE_TILINGS
+                 for g in CE_REGIMES] \
+    + [(r, v, "randn3", t, p) for (r, v), t in CE_TILINGS if len(t) > 1
+       for p in ("first", "last")]
+
+
+@functools.lru_cache(maxsize=None)
+def ce_tile_case(case):
+    """ce_inputs of the shape, with the target of row 3 on the first column
+    of the second tile and that of row 2 on the last column of the first
+    (one tile: columns 0 and V - 1)."""
+    rows, vocab, regime, tiles, peak = case
+    x, tg = ce_inputs(rows, vocab, regime)
+    x, tg = x.float(), tg.clone()
+    if peak is not None:
+        x[:, 1 if peak == "first" else vocab - 2] += 12.0
+    first = tiles[0] if len(tiles) > 1 else 0
+    tg[3], tg[2] = first, (first - 1) % vocab
+    x = x.to(torch.bfloat16)
+    a = (d(x), tg, -100, 1.0)
+    ex = cross_entropy(*a, mode="exact")
+    rd = cross_entropy(*a, mode="rounded")
+    keys = ("lse", "loss_sum", "count")
+    return dict(x=x, tg=tg, tiles=tiles, exact={k: ex[k] for k in keys},
+                rounded={k: rd[k] for k in keys})
+
+
+# ---------------------------------------------------------------------------
+# Every name the extension exports, and where its reference lives: a test
+# module, or the reason why the export computes nothing to hold against one
+# (tests/test_numerics_selfcheck.py::test_every_export_has_a_reference)
+# ---------------------------------------------------------------------------
+_ACC = "tests/test_kernel_accuracy_gpu.py"
+_OPS = "tests/test_ops_gpu.py"
+_BIAS = "tests/test_bias_grad_gpu.py"
+_GUARD = "tests/test_guarded_step_gpu.py"
+_PACKED = "tests/test_packed_merge_gpu.py"
+EXPORTS = {
+    "layernorm_fwd": _ACC, "layernorm_bwd": _ACC, "rmsnorm_fwd": _ACC,
+    "rmsnorm_bwd": _ACC, "gelu_fwd": _ACC, "gelu_bwd": _ACC,
+    "gelu_bwd_colsum": _BIAS, "swiglu_fwd": _ACC, "swiglu_bwd": _ACC,
+    "dropout_apply": _OPS,
+    "rng_tick": "not numeric: increments the int64 dropout step counter",
+    "accum_f32_into_bf16": _ACC, "delta_sub": _ACC, "axpy": _ACC,
+    "has_nan": _ACC, "l2norm_sq": _ACC, "adamw_step": _ACC,
+    "adamw_tick": _ACC,
+    "grad_sumsq_blocks": "not numeric: the number of partials the norm "
+                         "pass writes for a length",
+    "grad_sumsq_partials": _GUARD, "step_control": _GUARD,
+    "adamw_step_guarded": _GUARD, "colsum": _ACC, "weighted_merge": _ACC,
+    "grad_merge_weights": _ACC, "weighted_merge_packed": _PACKED,
+    "grad_merge_weights_packed": _PACKED, "axpy_packed": _PACKED,
+    "quantize_int8": _PACKED, "ce_fwd": _ACC, "ce_bwd": _ACC,
+    "ce_fwd_bwd": _ACC, "ce_chunk": _ACC, "ce_finalize": _ACC,
+    "head_loss_fwd": _ACC, "embedding_fwd": _ACC, "embedding_bwd": _ACC,
+    "kv_append": _ACC,
+    "i32_inc": _ACC, "gemv": _ACC, "rope_fwd": _ACC, "rope_bwd": _ACC,
+    "attn_fwd": _ACC, "attn_bwd": _ACC, "attn_bwd_packed": _ACC,
+    "attn_bwd_fused_enable": "not numeric: switches the single-tile fused "
+                             "backward on or off",
+    "attn_bwd_fused_calls": "not numeric: counts launches of the fused "
+                            "backward",
+    "attn_decode": _ACC,
+    "mfma_selftest_16": "not numeric: dumps the MFMA fragment layout "
+                        "(test_mfma_layout_16x16x32)",
+    "mfma_selftest_32": "not numeric: dumps the MFMA fragment layout "
+                        "(test_mfma_layout_32x32x16)",
+    "lt_linear_gelu_fwd": _OPS, "lt_dgrad_dgelu_bgrad": _OPS,
+    "lt_wgrad_bgradb": _OPS,
+}

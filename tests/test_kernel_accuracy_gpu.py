@@ -404,6 +404,305 @@ def test_axpy_accuracy(n, alpha):
             fp32_out=True)
 
 
+@pytest.mark.parametrize("n", [1, 3, 4, 4099])
+def test_delta_sub_equals_torch(n):
+    """One fp32 subtraction per element: torch.sub's bits (a scalar tail and
+    whole 4-wide vectors)."""
+    m = _ext()
+    g = torch.Generator().manual_seed(26)
+    w, base = torch.randn(n, generator=g), torch.randn(n, generator=g) * 3
+    out = torch.full((n,), float("nan"), device=DEV)
+    m.delta_sub(w.to(DEV), base.to(DEV), out)
+    assert torch.equal(out.cpu(), torch.sub(w, base))
+
+
+ACCUM_GUARD = 8     # elements in front of the slice: a 16 B aligned start
+
+
+def _accum_loop_n():
+    # 8 elements per lane and iteration: the capped grid goes round again
+    return _max_resident_blocks() * 256 * 8 + 4099
+
+
+@pytest.mark.parametrize("n,offs", [(1, (0, 1, 3)), (7, (0, 1, 3)),
+                                    (8, (0, 1, 3)), (4099, (0, 1, 3)),
+                                    ("loop", (1,))])
+def test_accum_f32_into_bf16_accuracy(n, offs):
+    """dst += src on a slice of a larger bf16 plane that starts 0, 1 and 3
+    elements off a 16 B boundary (a flat-grad view of any parameter); the
+    neighbours on both sides keep their bits."""
+    m = _ext()
+    n = _accum_loop_n() if n == "loop" else n
+    src = torch.randn(n, generator=torch.Generator().manual_seed(27))
+    for off in offs:
+        plane = N.randn_bf16(ACCUM_GUARD + off + n + 9, seed=28 + off)
+        lo, hi = ACCUM_GUARD + off, ACCUM_GUARD + off + n
+        exact = N.d(plane[lo:hi]) + N.d(src)
+        dev = plane.to(DEV)
+        assert dev.data_ptr() % 16 == 0
+        m.accum_f32_into_bf16(dev[lo:hi], src.to(DEV))
+        got = dev.cpu()
+        assert torch.equal(got[:lo].view(torch.int16),
+                           plane[:lo].view(torch.int16))
+        assert torch.equal(got[hi:].view(torch.int16),
+                           plane[hi:].view(torch.int16))
+        N.check("accum_f32_into_bf16", f"({n}, +{off})", "dst", got[lo:hi],
+                exact, N.bf16(exact), row_dim=None)
+
+
+# ---------------------------------------------------------------------------
+# Serving GEMV
+# ---------------------------------------------------------------------------
+@pytest.mark.parametrize("case", N.GEMV_CASES, ids=str)
+def test_gemv_accuracy(case):
+    m = _ext()
+    c = N.gemv_case(case)
+    b = (_empty(torch.bfloat16) if c["b"] is None else c["b"].to(DEV))
+    y = m.gemv(c["x"].to(DEV), c["w"].to(DEV), b)
+    assert y.shape == (case[0], case[1]) and y.dtype == torch.bfloat16
+    N.check("gemv", str(case), "y", y, c["exact"], c["rounded"])
+
+
+@pytest.mark.parametrize("M,K", [(1, 8200), (3, 2056)])
+def test_linear_routes_small_m_to_gemv(M, K):
+    """ops.linear under no_grad on a non-contiguous [M, 1, K] input returns
+    gemv's bits: the routing and its .contiguous() copy."""
+    from distributedtraining_amd import ops
+    m = _ext()
+    x, w, b = (t.to(DEV) for t in N.gemv_inputs(M, 5, K, "bf16", "randn"))
+    wide = torch.zeros(M, 1, K + 8, dtype=torch.bfloat16, device=DEV)
+    wide[..., :K] = x[:, None]
+    xv = wide[..., :K]
+    assert not xv.is_contiguous() or M == 1
+    with torch.no_grad():
+        y = ops.linear(xv, w, b)
+        y_nobias = ops.linear(xv, w)
+    assert y.shape == (M, 1, 5)
+    assert torch.equal(y.view(M, 5), m.gemv(x, w, b))
+    assert torch.equal(y_nobias.view(M, 5),
+                       m.gemv(x, w, _empty(torch.bfloat16)))
+
+
+# ---------------------------------------------------------------------------
+# Merge plane on fp32 deltas (the packed kernels are held bit-identical to
+# these in tests/test_packed_merge_gpu.py)
+# ---------------------------------------------------------------------------
+def _merge_run(c):
+    m = _ext()
+    out = torch.full((c["P"],), float("nan"), device=DEV)
+    m.weighted_merge(c["base"].to(DEV), c["deltas"].to(DEV), c["W"].to(DEV),
+                     c["offsets"].to(DEV), out)
+    return out
+
+
+@pytest.mark.parametrize("case", N.MERGE_CASES, ids=str)
+def test_weighted_merge_accuracy(case):
+    c = N.merge_case(case)
+    N.check("weighted_merge", str(case), "merged", _merge_run(c), c["exact"],
+            c["rounded"], row_dim=None, fp32_out=True)
+
+
+def test_weighted_merge_grid_loop_accuracy():
+    """A plane past MAX_RESIDENT_BLOCKS x 256 elements: the capped grid goes
+    round a second time."""
+    mrb = _max_resident_blocks()
+    c = N.merge_case_uncached(N.merge_loop_table(mrb), 3, "rand")
+    assert c["P"] > mrb * 256
+    N.check("weighted_merge", f"({c['P']}, 'loop')", "merged", _merge_run(c),
+            c["exact"], c["rounded"], row_dim=None, fp32_out=True)
+
+
+@pytest.mark.parametrize("case", N.GRADW_CASES, ids=str)
+def test_grad_merge_weights_accuracy(case):
+    """grad_W with ``merged`` given (the fp64 merge rounded to fp32), against
+    fp64 and an fp32 baseline that sums in the kernel's order. The d1e-3 and
+    d1e-5 regimes are the production ones, W = 1/N, where the summand
+    cancels: (base + d) - merged, the order grad_w_k used to have, measured
+    1e-5 to 1e-4 and 1e-3 to 8e-3 there against bounds of 1.5e-6 to 2e-5
+    (docs/test_accuracy.md)."""
+    m = _ext()
+    big = case[0] == "big"
+    c = N.gradw_case_uncached(case) if big else N.gradw_case(case)
+    gw = m.grad_merge_weights(c["g_in"].to(DEV), c["base"].to(DEV),
+                              c["deltas"].to(DEV), c["merged"].to(DEV),
+                              c["offsets"].to(DEV))
+    assert gw.shape == c["exact"].shape and gw.dtype == torch.float32
+    N.check("grad_merge_weights", str(case), "grad_W", gw, c["exact"],
+            c["rounded"], row_dim=None, fp32_out=True)
+
+
+def test_merge_bindings_reject_bad_arguments():
+    """Every bad argument raises before anything is launched."""
+    m = _ext()
+    P, n = 1024, 2
+    base = torch.zeros(P, device=DEV)
+    deltas = torch.zeros(n, P, device=DEV)
+    W = torch.ones(n, 1, device=DEV)
+    offs = torch.tensor([0, P], device=DEV)
+    out = torch.empty(P, device=DEV)
+    g = torch.ones(P, device=DEV)
+    m.weighted_merge(base, deltas, W, offs, out)
+    ref = m.grad_merge_weights(g, base + 1, deltas, base, offs)
+    assert ref.tolist() == [[float(P)], [float(P)]]
+    # an int32 table is converted, not read as int64
+    offs32 = torch.tensor([0, 1000, P], dtype=torch.int32, device=DEV)
+    W2 = torch.tensor([[1.0, 2.0], [0.0, 0.0]], device=DEV)
+    m.weighted_merge(base + 1, deltas, W2, offs32, out)
+    assert out[:1000].eq(1).all() and out[1000:].eq(2).all()
+    gw = m.grad_merge_weights(g, base + 1, deltas, base, offs32)
+    assert gw.tolist() == [[1000.0, 24.0], [1000.0, 24.0]]
+
+    def bad(fn, *a):
+        with pytest.raises(RuntimeError):
+            fn(*a)
+
+    wm, gm = m.weighted_merge, m.grad_merge_weights
+    bad(wm, base, deltas, torch.ones(1, n, device=DEV), offs, out)   # W^T
+    bad(wm, base, deltas, W[:1], offs, out)             # W rows != models
+    S = 1024                                    # [32, 1024] W: 128 KB of LDS
+    bad(wm, base, torch.zeros(32, P, device=DEV), torch.ones(32, S, device=DEV),
+        torch.arange(S + 1, device=DEV), out)
+    bad(wm, base, torch.zeros(33, P, device=DEV), torch.ones(33, 1, device=DEV),
+        offs, out)                              # more models than MAX_MODELS
+    bad(wm, base, deltas[:, :1000].contiguous(), W, offs, out)  # not [N, P]
+    bad(wm, base, deltas.view(-1), W, offs, out)
+    bad(wm, base, deltas, W, offs, out[:1000])          # out of another size
+    bad(wm, base.bfloat16(), deltas, W, offs, out)
+    bad(wm, base, deltas, W, offs.float(), out)         # float offsets
+    bad(wm, base, deltas, W, offs.view(1, 2), out)
+    bad(gm, g, base, deltas, base[:1000].contiguous(), offs)    # merged short
+    bad(gm, g, base, deltas, base.bfloat16(), offs)
+    bad(gm, g, base.bfloat16(), deltas, base, offs)
+    bad(gm, g[:1000].contiguous(), base, deltas, base, offs)    # g short
+    bad(gm, g.double(), base, deltas, base, offs)
+    bad(gm, g, base, deltas[:, :1000].contiguous(), base, offs)
+    bad(gm, g, base, deltas, base, offs.float())
+    bad(gm, g, base, deltas, base, torch.tensor([0, P + 1], device=DEV))
+    bad(gm, g, base, deltas, base, torch.tensor([0, 600, 500, P], device=DEV))
+
+
+# ---------------------------------------------------------------------------
+# ce_chunk + ce_finalize, the pipelined head's online softmax, driven
+# directly over column tiles
+# ---------------------------------------------------------------------------
+@pytest.mark.parametrize("how", ["fresh", "view"])
+@pytest.mark.parametrize("case", N.CE_TILE_CASES, ids=str)
+def test_ce_chunk_finalize_accuracy(case, how):
+    """fresh: every tile a contiguous tensor of its own, as _LMHeadCEFn
+    allocates them (leading dimension = tile width, odd where that is odd:
+    rows 2 B aligned under the 16 B loads). view: a column view of the full
+    logits (leading dimension V, v0 no multiple of 8)."""
+    m = _ext()
+    rows, vocab, _regime, tiles, _peak = case
+    c = N.ce_tile_case(case)
+    x, tg = c["x"].to(DEV), c["tg"].to(DEV)
+    mr = torch.full((rows,), float("-inf"), device=DEV)
+    sr = torch.zeros(rows, device=DEV)
+    tl = torch.zeros(rows, device=DEV)
+    v0 = 0
+    for wd in tiles:
+        tile = x[:, v0:v0 + wd]
+        if how == "fresh":
+            tile = tile.contiguous()
+        assert tile.stride() == ((wd if how == "fresh" else vocab), 1)
+        m.ce_chunk(tile, tg, v0, tl, mr, sr)
+        v0 += wd
+    loss_sum, lse, count = m.ce_finalize(tg, mr, sr, tl, -100)
+    ex, rd = c["exact"], c["rounded"]
+    name = f"{case[:3]}/{'+'.join(map(str, tiles))}/{case[4]}/{how}"
+    fails = []
+    for a, kw in (
+            (("lse", lse, ex["lse"], rd["lse"]), {}),
+            (("loss_sum", loss_sum.reshape(1), ex["loss_sum"].reshape(1),
+              rd["loss_sum"].reshape(1)),
+             dict(ulp_of=ex["lse"][c["tg"] != -100]))):
+        try:
+            N.check("ce_chunk", name, *a, row_dim=None, fp32_out=True, **kw)
+        except AssertionError as e:
+            fails.append(str(e))
+    assert not fails, "\n".join(fails)
+    assert int(count) == ex["count"]
+    # the recorded target logit is the bf16 input, bit for bit; ignored rows
+    # keep their initial 0
+    valid = c["tg"] != -100
+    want = torch.zeros(rows)
+    want[valid] = c["x"].float()[valid].gather(
+        1, c["tg"][valid][:, None])[:, 0]
+    assert torch.equal(tl.cpu(), want)
+
+
+# ---------------------------------------------------------------------------
+# KV-cache append at a device position
+# ---------------------------------------------------------------------------
+def _sentinel(shape, add):
+    n = 1
+    for s in shape:
+        n *= s
+    return ((torch.arange(n) % 251) + add).to(torch.bfloat16).view(shape)
+
+
+# (B, H, Hk, Lmax, D); the last has B Hk D > 1024 x 256: the capped grid loops
+@pytest.mark.parametrize("shape", [(2, 4, 2, 5, 64), (3, 2, 2, 4, 128),
+                                   (33, 64, 64, 2, 128)], ids=str)
+def test_kv_append_and_i32_inc(shape):
+    """k / v as strided slices of one packed projection into sentinel-filled
+    caches at device row 0, a middle row and Lmax - 1: exactly the addressed
+    rows change and equal the source; after i32_inc the next append lands
+    one row on."""
+    m = _ext()
+    B, H, Hk, Lmax, D = shape
+    E, kvd = H * D, Hk * D
+
+    def proj(seed):
+        p = N.randn_bf16(B, 1, E + 2 * kvd, seed=seed).to(DEV)
+        k, v = p[..., E:E + kvd], p[..., E + kvd:]
+        assert k.stride(0) == E + 2 * kvd
+        return k, v
+
+    k0, v0 = proj(30)
+    k1, v1 = proj(31)
+    sk, sv = _sentinel((B, Hk, Lmax, D), 0), _sentinel((B, Hk, Lmax, D), 300)
+    for p0 in sorted({0, Lmax // 2, Lmax - 1}):
+        kc, vc = sk.to(DEV), sv.to(DEV)
+        pos = _i32(p0)
+        m.kv_append(k0, v0, kc, vc, pos)
+        want_k, want_v = sk.clone(), sv.clone()
+        want_k[:, :, p0] = k0.cpu().reshape(B, Hk, D)
+        want_v[:, :, p0] = v0.cpu().reshape(B, Hk, D)
+        assert int(pos) == p0
+        assert torch.equal(kc.cpu(), want_k) and torch.equal(vc.cpu(), want_v)
+        m.i32_inc(pos)
+        assert int(pos) == p0 + 1
+        if p0 + 1 < Lmax:
+            m.kv_append(k1, v1, kc, vc, pos)
+            want_k[:, :, p0 + 1] = k1.cpu().reshape(B, Hk, D)
+            want_v[:, :, p0 + 1] = v1.cpu().reshape(B, Hk, D)
+            assert torch.equal(kc.cpu(), want_k)
+            assert torch.equal(vc.cpu(), want_v)
+
+
+def test_kv_append_rejects_bad_caches():
+    m = _ext()
+    B, Hk, Lmax, D = 2, 2, 4, 64
+    p = torch.zeros(B, 1, 4 * Hk * D, dtype=torch.bfloat16, device=DEV)
+    k, v = p[..., :Hk * D], p[..., Hk * D:2 * Hk * D]
+    kc = torch.zeros(B, Hk, Lmax, D, dtype=torch.bfloat16, device=DEV)
+    vc = torch.zeros_like(kc)
+    pos = _i32(1)
+    m.kv_append(k, v, kc, vc, pos)
+    wide = torch.zeros(B, Hk, 2 * Lmax, D, dtype=torch.bfloat16, device=DEV)
+    for bad_k, bad_v in ((kc.float(), vc.float()),          # not bf16
+                         (kc, vc.float()),
+                         (wide[:, :, ::2], wide[:, :, ::2]),   # row stride 2D
+                         (kc.transpose(2, 3), vc.transpose(2, 3)),
+                         (kc, torch.zeros_like(wide)),          # other shape
+                         (kc[:1], vc[:1])):                     # other batch
+        with pytest.raises(RuntimeError):
+            m.kv_append(k, v, bad_k, bad_v, pos)
+    with pytest.raises(RuntimeError):       # rows of another width
+        m.kv_append(p[..., :D], p[..., D:2 * D], kc, vc, pos)
+
+
 @pytest.mark.parametrize("n", [3, 4099, (1 << 21) + 3])
 def test_has_nan_tail_and_last_vector(n):
     """The NaN in the scalar tail (n is no multiple of the 4-wide vector),

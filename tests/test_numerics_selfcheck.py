@@ -425,3 +425,221 @@ def test_flat_references_feasible():
     ex, rd = N.axpy(w, y, -0.37), N.axpy(w, y, -0.37, "rounded")
     assert N.passes(rd, ex, rd, None, None, True)
     assert not N.passes(N.axpy(w, y, 1.0), ex, rd, None, None, True)
+
+
+# ---------------------------------------------------------------------------
+# Serving GEMV
+# ---------------------------------------------------------------------------
+@pytest.mark.parametrize("case", N.GEMV_CASES, ids=str)
+def test_gemv_rounded_feasible_and_mutants_rejected(case):
+    """A mutant must be rejected wherever it changes the value, with these
+    exceptions, each for the reason given.
+
+    drop_last8, and drop_last_chunk where the last chunk IS those 8 elements
+    (K = 4104 = KC + 8 or 2 KC + 8): 8 of K >= 4096 products are sqrt(8 / K)
+    <= 4.4 % of the dot product's rms, one to two bf16 steps of the result;
+    on the one or five numbers of such a row that is inside 3 x the floor as
+    often as not. It is required up to K = 2056 and in the cancelling regime
+    at every K, where each of the 8 products is 8 / (K / 2) x 50 of the
+    result. Under a bias of 100 x the product nothing about 8 elements shows.
+
+    bf16_between_chunks: one more bf16 rounding, of a partial sum no larger
+    than the result, is below 3 x the floor in the randn regime. The
+    cancelling regime is there for it: the partial at the chunk boundary is
+    50 x the result at (1, 14336) and (4, 4104). At (2, 4104) and (3, 2056)
+    the boundary falls 8 elements before the end, where the two halves have
+    cancelled already.
+
+    skip_last_col at (1, 2051, 64): one column in 2051 that happens to hold
+    a value of a fifth of the rms; (4, 2051, 64) has four rows of it."""
+    M, Ncol, K, bias, regime = case
+    c = N.gemv_case(case)
+    ex, rd = c["exact"], c["rounded"]
+    assert N.passes(rd, ex, rd)
+
+    def rejected(**mut):
+        return not N.passes(N.gemv(*c["args"], mut=mut), ex, rd)
+
+    last = K - ((K - 1) // N.gemv_kc(M)) * N.gemv_kc(M)
+    eight = regime == "cancel" or (K <= 2056 and bias != "x100")
+    if eight:
+        assert rejected(drop_last8=True)
+    if last > 8 or eight:
+        assert rejected(drop_last_chunk=True)
+    if bias != "none":
+        assert rejected(no_bias=True)
+    if case in ((1, 5, 14336, "none", "cancel"), (4, 5, 4104, "none", "cancel")):
+        assert rejected(bf16_between_chunks=True)
+    if M > 1:
+        assert rejected(row_shift=True)
+    if case != (1, 2051, 64, "bf16", "randn"):
+        assert rejected(skip_last_col=True)
+
+
+# ---------------------------------------------------------------------------
+# Merge plane
+# ---------------------------------------------------------------------------
+_F32 = (None, None, True)       # row_dim, live, fp32_out of an fp32 plane
+
+
+@pytest.mark.parametrize("case", N.MERGE_CASES, ids=str)
+def test_weighted_merge_rounded_feasible_and_mutants_rejected(case):
+    """Every mutant is rejected wherever it changes the value in exact
+    arithmetic. It does not: a neighbouring segment's weight and W read as
+    [seg, i] under uniform W, with one model, or with one segment; base
+    added once where the columns of W sum to 1 (uniform, signed: the same
+    number up to fp32 rounding)."""
+    table, n, wkind = case
+    c = N.merge_case(case)
+    ex, rd = c["exact"], c["rounded"]
+    assert N.passes(rd, ex, rd, *_F32)
+
+    def rejected(**mut):
+        return not N.passes(N.weighted_merge(*c["args"], mut=mut), ex, rd,
+                            *_F32)
+
+    assert rejected(drop_last_model=True)
+    varied = wkind == "rand" or (wkind == "signed" and n > 1)
+    segs = sum(1 for s in N.MERGE_TABLES[table] if s)
+    if varied and segs > 1:
+        assert rejected(boundary_prev_weight=True)
+        if n > 1:
+            assert rejected(w_transposed=True)
+    if wkind == "rand":
+        assert rejected(base_once=True)
+
+
+def test_weighted_merge_loop_plane_feasible():
+    mrb = N.max_resident_blocks()
+    t = N.merge_case_uncached(N.merge_loop_table(mrb), 3, "rand")
+    assert t["P"] > mrb * 256
+    assert N.passes(t["rounded"], t["exact"], t["rounded"], *_F32)
+
+
+def _np32(t):
+    return N.d(t).to(torch.float32).numpy()
+
+
+@pytest.mark.parametrize("case", N.GRADW_CASES, ids=str)
+def test_grad_w_rounded_feasible_and_mutants_rejected(case):
+    """The summand order grad_w_k had, (base + d) - merged, summed in the
+    kernel's own lane order, is rejected in both cancelling regimes (it is
+    the same number where W does not cancel). The other mutants are rejected
+    wherever they change the value: next_seg does not with one segment."""
+    table, _n, regime, gd = case
+    c = N.gradw_case(case) if table != "big" else N.gradw_case_uncached(case)
+    ex, rd = c["exact"], c["rounded"]
+    assert N.passes(rd, ex, rd, *_F32)
+    parent = torch.from_numpy(N.grad_w_fp32(
+        _np32(c["g_in"]), _np32(c["base"]), _np32(c["deltas"]),
+        _np32(c["merged"]), c["offsets"], order="parent")).to(N.F64)
+    e_par, e_rd = N.errors(parent, ex, None), N.errors(rd, ex, None)
+    print(f"[selfcheck] grad_W {case}: (base+d)-merged {e_par[0]:.2e}/"
+          f"{e_par[1]:.2e}, (base-merged)+d {e_rd[0]:.2e}/{e_rd[1]:.2e}")
+    if regime in ("d1e-3", "d1e-5"):
+        assert not N.passes(parent, ex, rd, *_F32)
+    else:
+        assert N.passes(parent, ex, rd, *_F32)
+
+    def rejected(**mut):
+        return not N.passes(N.grad_merge_weights(*c["args"], mut=mut), ex,
+                            rd, *_F32)
+
+    assert rejected(no_merged=True)
+    assert rejected(drop_seg_last=True)
+    if len(N.MERGE_TABLES[table]) > 1:
+        assert rejected(next_seg=True)
+    if gd == "bf16":
+        # bf16 g read as the fp32 plane it was rounded from
+        a = (N.d(c["g_src"]),) + c["args"][1:]
+        assert not N.passes(N.grad_merge_weights(*a), ex, rd, *_F32)
+
+
+def test_lane_sum32_is_the_kernel_order():
+    """256 strided serial fp32 chains, then a serial fold, on numbers where
+    the order shows: 1 followed by 2^-24 s gives 1 in a chain of its own
+    and more in any pairwise order."""
+    import numpy as np
+    t = np.zeros(512, np.float32)
+    t[0] = 1.0
+    t[256] = 2.0 ** -24          # same lane as t[0]: lost
+    t[1], t[257] = 2.0 ** -24, 2.0 ** -24     # lane 1: kept, 2^-23
+    assert float(N.lane_sum32(t)) == 1.0 + 2.0 ** -23
+    assert float(N.lane_sum32(np.zeros(0, np.float32))) == 0.0
+
+
+# ---------------------------------------------------------------------------
+# ce_chunk + ce_finalize
+# ---------------------------------------------------------------------------
+@pytest.mark.parametrize("case", N.CE_TILE_CASES, ids=str)
+def test_ce_tiles_model_and_mutants(case):
+    """The tile-by-tile model equals the one-shot reference, and its mutants
+    are rejected, except: no_rescale with one tile, or where the maximum of
+    every row arrives with the first tile (peak first at (5, 7); the other
+    shapes have row 1's target, 30 above the rest, in a later tile);
+    drop_tail where no tile has a tail (widths 640, 360, 1000), and at
+    (8, 50257), whose tail is one column in 50257: 2e-5 of the row's sum,
+    below the fp32 bound of an lse of 10 to 90."""
+    rows, vocab, _regime, tiles, peak = case
+    c = N.ce_tile_case(case)
+    ex, rd = c["exact"], c["rounded"]
+    x, tg = N.d(c["x"]), c["tg"]
+    u = ex["lse"][tg != -100]
+    got = N.ce_tiles(x, tg, tiles, -100)
+    assert torch.allclose(got["lse"], ex["lse"], rtol=1e-12, atol=0)
+    assert float(got["loss_sum"]) == pytest.approx(float(ex["loss_sum"]),
+                                                   rel=1e-10)
+    assert got["count"] == ex["count"]
+    valid = tg != -100
+    assert torch.equal(got["tlogit"][valid],
+                       x[valid].gather(1, tg[valid][:, None])[:, 0])
+    assert N.passes(rd["lse"], ex["lse"], rd["lse"], *_F32)
+    assert N.passes(rd["loss_sum"].reshape(1), ex["loss_sum"].reshape(1),
+                    rd["loss_sum"].reshape(1), None, None, True, u)
+
+    def rej(**mut):
+        g = N.ce_tiles(x, tg, tiles, -100, mut=mut)
+        out = set()
+        if not N.passes(g["lse"], ex["lse"], rd["lse"], *_F32):
+            out.add("lse")
+        if not N.passes(g["loss_sum"].reshape(1), ex["loss_sum"].reshape(1),
+                        rd["loss_sum"].reshape(1), None, None, True, u):
+            out.add("loss_sum")
+        if g["count"] != ex["count"]:
+            out.add("count")
+        if not torch.equal(g["tlogit"], got["tlogit"]):
+            out.add("tlogit")
+        return out
+
+    if len(tiles) > 1 and not (vocab == 7 and peak == "first"):
+        assert "lse" in rej(no_rescale=True)
+    assert {"loss_sum", "tlogit"} <= rej(v0_off=True)
+    if any(w % 8 for w in tiles) and vocab != 50257:
+        assert {"lse", "loss_sum"} <= rej(drop_tail=True)
+    assert {"loss_sum", "count"} <= rej(count_ignored=True)
+
+
+# ---------------------------------------------------------------------------
+# Completeness: every export of the extension has an entry in N.EXPORTS
+# ---------------------------------------------------------------------------
+def test_every_export_has_a_reference():
+    import os
+    import re
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    hip = os.path.join(root, "distributedtraining_amd", "ops", "hip")
+    names = []
+    for src in ("bindings.cpp", "lt_fused.cpp"):
+        with open(os.path.join(hip, src)) as f:
+            names += re.findall(r'm\.def\(\s*"(\w+)"', f.read())
+    assert len(names) > 50 and len(set(names)) == len(names)
+    missing = [n for n in names if n not in N.EXPORTS]
+    assert not missing, f"exports without an entry in _numerics.EXPORTS: " \
+                        f"{missing}"
+    stale = [n for n in N.EXPORTS if n not in names]
+    assert not stale, f"entries of _numerics.EXPORTS that are no export: " \
+                      f"{stale}"
+    for name, where in N.EXPORTS.items():
+        if where.startswith("tests/"):
+            assert os.path.isfile(os.path.join(root, where)), (name, where)
+        else:
+            assert where.startswith("not numeric: "), (name, where)
