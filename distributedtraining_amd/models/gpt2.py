@@ -50,7 +50,7 @@ class GPT2Block(nn.Module):
         self.mlp_proj_w = nn.Parameter(torch.empty(E, 4 * E))
         self.mlp_proj_b = nn.Parameter(torch.zeros(E))
 
-    def forward(self, x: torch.Tensor, pending=None, kvlen=None):
+    def forward(self, x: torch.Tensor, pending=None, kvlen=None, doc=None):
         """Residual-join-fused layout: ``pending`` is the previous
         sub-layer's un-added branch output; every LayerNorm consumes it
         via ops.add_layer_norm (one kernel produces both the new residual
@@ -59,6 +59,7 @@ class GPT2Block(nn.Module):
 
         ``kvlen`` (int32 [B], optional): right-padding mask — the
         reference's attention_mask path (training_manager.py:380-385).
+        ``doc``: (q_lo, k_hi) document mask of a packed batch, or None.
         Residual branches get counter-RNG dropout in train mode
         (transformers resid_pdrop/attn_pdrop semantics), FUSED into the
         add_layer_norm join that consumes each branch (zero extra HBM
@@ -75,15 +76,39 @@ class GPT2Block(nn.Module):
             s, h = ops.add_layer_norm(x, pending, self.ln_1_w, self.ln_1_b,
                                       p_drop=rp, site=i3)
         qkv = ops.linear(h, self.attn_qkv_w, self.attn_qkv_b)
+        q_lo, k_hi = doc if doc is not None else (None, None)
         o = ops.qkv_attention(qkv, self.n_head, kvlen=kvlen,
                               p_drop=self.attn_pdrop if t else 0.0,
-                              site=i3 + 1)
+                              site=i3 + 1, q_lo=q_lo, k_hi=k_hi)
         a = ops.linear(o, self.attn_proj_w, self.attn_proj_b)
         s2, h2 = ops.add_layer_norm(s, a, self.ln_2_w, self.ln_2_b,
                                     p_drop=rp, site=i3 + 2)
         m = ops.mlp_gelu(h2, self.mlp_fc_w, self.mlp_fc_b,
                          self.mlp_proj_w, self.mlp_proj_b)
         return s2, m
+
+
+def doc_bounds(doc_start: Optional[torch.Tensor]):
+    """(q_lo, k_hi) for the attention of every block, derived once per
+    forward; None without a document layout."""
+    if doc_start is None:
+        return None
+    if doc_start.dtype != torch.int32 or doc_start.dim() != 2:
+        raise ValueError("doc_start must be an int32 [B, S] tensor")
+    doc_start = doc_start.contiguous()
+    return doc_start, ops.q_lo_inverse(doc_start)
+
+
+def mask_doc_targets(tgt: torch.Tensor,
+                     doc_start: Optional[torch.Tensor]) -> torch.Tensor:
+    """Shifted targets ``labels[:, 1:]`` with every document's first token
+    ignored (-100): it is not predicted from the previous document. The
+    separator that ends a document stays a target."""
+    if doc_start is None:
+        return tgt
+    S = doc_start.shape[1]
+    nxt = torch.arange(1, S, dtype=doc_start.dtype, device=doc_start.device)
+    return tgt.masked_fill(doc_start[:, 1:] == nxt, -100)
 
 
 @dataclass
@@ -125,22 +150,31 @@ class GPT2LM(nn.Module):
                 attention_mask: Optional[torch.Tensor] = None,
                 labels: Optional[torch.Tensor] = None,
                 return_logits: Optional[bool] = None,
-                loss_only: bool = False) -> CausalLMOutput:
+                loss_only: bool = False,
+                doc_start: Optional[torch.Tensor] = None) -> CausalLMOutput:
         """``attention_mask`` ([B,S] of 1/0, right-padded — the reference's
         collate, neurons/miner.py:95-99): padded keys are masked out of
         attention AND padded label positions are ignored in the loss
         (set to -100 → the CE kernel's ignore_index path). The reference
         passes the mask but lets pad targets into the loss; ignoring them
-        is the corrected semantics (round-1 verdict item #1)."""
+        is the corrected semantics (round-1 verdict item #1).
+
+        ``doc_start`` (int32 [B,S], packed sequences): index of the first
+        token of the document holding each token. Attention stays inside a
+        document, positions restart at its start, and the first token of a
+        document is not a target of the previous one, so a packed row
+        computes what its documents would separately."""
         kvlen = None
         if attention_mask is not None:   # int32 explicitly: torch promotes
             kvlen = attention_mask.sum(dim=1, dtype=torch.int32).clamp_(min=1)
-        x = ops.embedding_fwd(input_ids, self.wte, self.wpe)
+        doc = doc_bounds(doc_start)   # once per forward, for every block
+        x = ops.embedding_fwd(input_ids, self.wte, self.wpe,
+                              doc_start=doc_start)
         x = ops.dropout(x, self.cfg.embd_pdrop, site=0,
                         training=self.training)
         pending = None
         for blk in self.blocks:
-            x, pending = blk(x, pending, kvlen=kvlen)
+            x, pending = blk(x, pending, kvlen=kvlen, doc=doc)
         if pending is None:
             x = ops.layer_norm(x, self.ln_f_w, self.ln_f_b)
         else:
@@ -157,6 +191,7 @@ class GPT2LM(nn.Module):
         tgt = labels[:, 1:]
         if attention_mask is not None:
             tgt = tgt.masked_fill(attention_mask[:, 1:] == 0, -100)
+        tgt = mask_doc_targets(tgt, doc_start)
         B, S = input_ids.shape
         if loss_only:
             # no-grad consumers (validator scoring): fused MFMA head + online

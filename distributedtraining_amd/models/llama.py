@@ -19,7 +19,7 @@ import torch.nn as nn
 
 from .. import ops
 from ..config import ModelConfig
-from .gpt2 import CausalLMOutput
+from .gpt2 import CausalLMOutput, doc_bounds, mask_doc_targets
 
 
 def rope_tables(n_pos: int, head_dim: int, theta: float,
@@ -59,9 +59,12 @@ class LlamaBlock(nn.Module):
         self.down_w = nn.Parameter(torch.empty(E, I))
 
     def forward(self, x: torch.Tensor, cos: torch.Tensor,
-                sin: torch.Tensor, pending=None, kvlen=None):
+                sin: torch.Tensor, pending=None, kvlen=None, doc=None):
         """Residual-join-fused layout (see gpt2.GPT2Block.forward):
-        returns (stream, pending). kvlen: right-padding mask (int32 [B])."""
+        returns (stream, pending). kvlen: right-padding mask (int32 [B]).
+        doc: (q_lo, k_hi) document mask of a packed batch. The rotary
+        positions are not restarted: scores depend on position differences
+        only, the same inside a document wherever it sits in the row."""
         B, S, E = x.shape
         D = self.head_dim
         if pending is None:
@@ -78,7 +81,8 @@ class LlamaBlock(nn.Module):
             .view(B, S, self.n_kv, D).transpose(1, 2)
         q = ops.rope(q, cos, sin)
         k = ops.rope(k, cos, sin)
-        o = ops.causal_attention(q, k, v, kvlen=kvlen)
+        q_lo, k_hi = doc if doc is not None else (None, None)
+        o = ops.causal_attention(q, k, v, kvlen=kvlen, q_lo=q_lo, k_hi=k_hi)
         o = o.transpose(1, 2).reshape(B, S, E)
         a = ops.linear(o, self.o_w)
         s2, h2 = ops.add_rms_norm(s, a, self.mlp_norm_w, self.norm_eps)
@@ -135,17 +139,22 @@ class LlamaLM(nn.Module):
                 attention_mask: Optional[torch.Tensor] = None,
                 labels: Optional[torch.Tensor] = None,
                 return_logits: Optional[bool] = None,
-                loss_only: bool = False) -> CausalLMOutput:
+                loss_only: bool = False,
+                doc_start: Optional[torch.Tensor] = None) -> CausalLMOutput:
+        """``doc_start``: packed-sequence document layout, as in
+        gpt2.GPT2LM.forward (attention mask and label rule; no position
+        restart is needed with rotary embeddings)."""
         S = input_ids.shape[1]
         cos = self.rope_cos[:S]
         sin = self.rope_sin[:S]
         kvlen = None
         if attention_mask is not None:   # right-padded mask → key prefix
             kvlen = attention_mask.sum(dim=1, dtype=torch.int32).clamp_(min=1)
+        doc = doc_bounds(doc_start)   # once per forward
         x = ops.embedding_fwd(input_ids, self.tok_emb, None)
         pending = None
         for blk in self.blocks:
-            x, pending = blk(x, cos, sin, pending, kvlen=kvlen)
+            x, pending = blk(x, cos, sin, pending, kvlen=kvlen, doc=doc)
         if pending is None:
             x = ops.rms_norm(x, self.final_norm_w, self.cfg.norm_eps)
         else:
@@ -156,6 +165,7 @@ class LlamaLM(nn.Module):
         tgt = labels[:, 1:]
         if attention_mask is not None:   # pad targets ignored (-100)
             tgt = tgt.masked_fill(attention_mask[:, 1:] == 0, -100)
+        tgt = mask_doc_targets(tgt, doc_start)
         B = input_ids.shape[0]
         if loss_only:
             # no-grad consumers (validator scoring): fused MFMA head + online

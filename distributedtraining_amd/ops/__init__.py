@@ -34,7 +34,7 @@ __all__ = [
     "qkv_attention", "linear", "mlp_gelu", "add_layer_norm",
     "add_rms_norm",
     "cross_entropy_loss", "lm_head_ce", "lm_head_loss",
-    "embedding_fwd",
+    "embedding_fwd", "check_q_lo", "check_doc_start", "q_lo_inverse",
     "decode_attention", "rope", "adamw_step", "delta_sub", "axpy_",
     "weighted_merge",
     "grad_merge_weights", "has_nan", "l2norm",
@@ -554,6 +554,65 @@ def _dense_last(t: torch.Tensor) -> torch.Tensor:
     return t if t.stride(-1) == 1 else t.contiguous()
 
 
+def check_q_lo(q_lo: torch.Tensor) -> torch.Tensor:
+    """Validate a document-mask lower bound on the host: int32 [B, S] with
+    0 <= q_lo[b, q] <= q, non-decreasing along q. Raises ValueError. Reads
+    the values (a sync on a GPU tensor): for the CPU path, the packer and
+    tests — the GPU kernels clamp instead of checking."""
+    if not isinstance(q_lo, torch.Tensor) or q_lo.dtype != torch.int32:
+        raise ValueError("q_lo must be an int32 tensor")
+    if q_lo.dim() != 2:
+        raise ValueError(f"q_lo must be [B, S], got {tuple(q_lo.shape)}")
+    S = q_lo.shape[1]
+    idx = torch.arange(S, dtype=torch.int32, device=q_lo.device)
+    if bool((q_lo < 0).any()):
+        raise ValueError("q_lo has negative entries")
+    if bool((q_lo > idx).any()):
+        raise ValueError("q_lo[b, q] must be <= q")
+    if S > 1 and bool((q_lo[:, 1:] < q_lo[:, :-1]).any()):
+        raise ValueError("q_lo must be non-decreasing along the sequence")
+    return q_lo
+
+
+def check_doc_start(doc_start: torch.Tensor) -> torch.Tensor:
+    """:func:`check_q_lo`, and that the tensor is a document layout: every
+    value names a column that starts a document (doc_start there equals the
+    column). What the embedding needs; raises ValueError."""
+    check_q_lo(doc_start)
+    at_start = torch.gather(doc_start, 1, doc_start.long())
+    if bool((at_start != doc_start).any()):
+        raise ValueError("doc_start is not a document layout: "
+                         "doc_start[b, doc_start[b, s]] must equal "
+                         "doc_start[b, s]")
+    return doc_start
+
+
+def q_lo_inverse(q_lo: torch.Tensor) -> torch.Tensor:
+    """k_hi[b, k] = #{q : q_lo[b, q] <= k}: one past the last query that
+    sees key k, the attention backward's loop bound. q_lo is non-decreasing,
+    so this is one searchsorted over the rows: on the device, no host sync,
+    capturable. Derive it once per batch and hand it to every layer."""
+    B, S = q_lo.shape
+    keys = torch.arange(S, dtype=torch.int32, device=q_lo.device)
+    return torch.searchsorted(q_lo.contiguous(), keys.expand(B, S).contiguous(),
+                              right=True, out_int32=True)
+
+
+def _doc_bounds(q_lo, k_hi, like: torch.Tensor):
+    """(q_lo, k_hi) as the bindings take them: int32 contiguous on
+    ``like``'s device, k_hi derived when the caller did not."""
+    if q_lo is None:
+        return None, None
+    B, S = like.shape[0], like.shape[-2] if like.dim() == 4 else like.shape[1]
+    if q_lo.dtype != torch.int32 or tuple(q_lo.shape) != (B, S):
+        raise ValueError(f"q_lo must be int32 [{B}, {S}], got {q_lo.dtype} "
+                         f"{tuple(q_lo.shape)}")
+    q_lo = q_lo.contiguous()
+    if k_hi is None:
+        k_hi = q_lo_inverse(q_lo)
+    return q_lo, k_hi
+
+
 def _mask_and_counter(kvlen, like: torch.Tensor):
     """The kvlen tensor the bindings expect (empty = no mask) and the
     dropout step counter of ``like``'s device."""
@@ -564,27 +623,29 @@ def _mask_and_counter(kvlen, like: torch.Tensor):
 
 class _AttnFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, q, k, v, scale, kvlen, p_drop, site):
+    def forward(ctx, q, k, v, scale, kvlen, p_drop, site, q_lo=None,
+                k_hi=None):
         m = require_ext()
         q, k, v = _dense_last(q), _dense_last(k), _dense_last(v)
         kv, rng = _mask_and_counter(kvlen, q)
-        o_bshd, lse = m.attn_fwd(q, k, v, scale, kv, rng, site, p_drop)
-        ctx.save_for_backward(q, k, v, o_bshd, lse, kv, rng)
+        o_bshd, lse = m.attn_fwd(q, k, v, scale, kv, rng, site, p_drop,
+                                 q_lo)
+        ctx.save_for_backward(q, k, v, o_bshd, lse, kv, rng, q_lo, k_hi)
         ctx.attn_args = (scale, site, p_drop)
         return o_bshd.permute(0, 2, 1, 3)  # [B,H,S,D] view, zero-copy
 
     @staticmethod
     def backward(ctx, do):
         m = require_ext()
-        q, k, v, o_bshd, lse, kv, rng = ctx.saved_tensors
+        q, k, v, o_bshd, lse, kv, rng, q_lo, k_hi = ctx.saved_tensors
         scale, site, p_drop = ctx.attn_args
         dq_bshd, dk, dv = m.attn_bwd(_dense_last(do), q, k, v, o_bshd, lse,
-                                     scale, kv, rng, site, p_drop)
+                                     scale, kv, rng, site, p_drop, q_lo, k_hi)
         return (dq_bshd.permute(0, 2, 1, 3), dk, dv, None, None, None,
-                None)
+                None, None, None)
 
 
-def _attn_ref(q, k, v, scale, kvlen, p_drop, site):
+def _attn_ref(q, k, v, scale, kvlen, p_drop, site, q_lo=None):
     """CPU gold: explicit masked softmax attention with the SAME padding
     and dropout semantics the HIP kernels implement (mask from the shared
     RNG chain, so GPU tests compare bit-identical masks). fp32 math;
@@ -602,6 +663,9 @@ def _attn_ref(q, k, v, scale, kvlen, p_drop, site):
     if kvlen is not None:
         allowed = allowed & (idx[None, None, None, :]
                              < kvlen.view(B, 1, 1, 1).to(torch.long))
+    if q_lo is not None:   # document mask: keys from q's document start on
+        allowed = allowed & (idx[None, None, None, :]
+                             >= q_lo.view(B, 1, S, 1).to(torch.long))
     A = torch.softmax(scores.masked_fill(~allowed, float("-inf")), dim=-1)
     if p_drop > 0.0:
         keep = droprng.attn_keep_mask(B * H, S, S,
@@ -614,7 +678,9 @@ def _attn_ref(q, k, v, scale, kvlen, p_drop, site):
 def causal_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
                      scale: Optional[float] = None,
                      kvlen: Optional[torch.Tensor] = None,
-                     p_drop: float = 0.0, site: int = 0) -> torch.Tensor:
+                     p_drop: float = 0.0, site: int = 0,
+                     q_lo: Optional[torch.Tensor] = None,
+                     k_hi: Optional[torch.Tensor] = None) -> torch.Tensor:
     """softmax(q kᵀ · scale + causal_mask) v over [B, H, S, D] tensors.
 
     GQA: k/v may have fewer heads (H_kv dividing H) — handled natively by
@@ -625,15 +691,25 @@ def causal_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
     iff j < kvlen[b] (the reference's attention_mask semantics,
     training_manager.py:380-385). ``p_drop``/``site``: attention-prob
     dropout from the counter RNG (transformers attn_pdrop).
+
+    ``q_lo`` (int32 [B, S]): document mask of packed sequences — key k is
+    visible to query q iff q_lo[b, q] <= k as well; q_lo[b, s] is the first
+    token of the document that holds s (contract: :func:`check_q_lo`; the
+    GPU path does not validate, the kernels clamp). ``k_hi``: its inverse
+    (:func:`q_lo_inverse`), derived here unless the caller did it once for
+    all layers.
     """
     if scale is None:
         scale = 1.0 / math.sqrt(q.shape[-1])
     if use_hip(q):
-        return _AttnFn.apply(q, k, v, scale, kvlen, p_drop, site)
-    if kvlen is None and p_drop <= 0.0:
+        q_lo, k_hi = _doc_bounds(q_lo, k_hi, q)
+        return _AttnFn.apply(q, k, v, scale, kvlen, p_drop, site, q_lo, k_hi)
+    if kvlen is None and p_drop <= 0.0 and q_lo is None:
         return F.scaled_dot_product_attention(q, k, v, is_causal=True,
                                               scale=scale, enable_gqa=True)
-    return _attn_ref(q, k, v, scale, kvlen, p_drop, site)
+    if q_lo is not None:
+        check_q_lo(q_lo)
+    return _attn_ref(q, k, v, scale, kvlen, p_drop, site, q_lo)
 
 
 # --------------------------------------------------------------------------
@@ -659,22 +735,23 @@ def _qkv_views(t: torch.Tensor, H: int, Hk: int, D: int,
 
 class _QKVAttnFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, qkv, H, Hk, scale, kvlen, p_drop, site):
+    def forward(ctx, qkv, H, Hk, scale, kvlen, p_drop, site, q_lo=None,
+                k_hi=None):
         m = require_ext()
         B, S, Fdim = qkv.shape
         D = Fdim // (H + 2 * Hk)
         q, k, v = _qkv_views(qkv, H, Hk, D)
         kv, rng = _mask_and_counter(kvlen, qkv)
         o_bshd, lse = m.attn_fwd(q, k, v, scale, kv, rng, site,
-                                 p_drop)   # [B,S,H,D] contiguous
-        ctx.save_for_backward(qkv, o_bshd, lse, kv, rng)
+                                 p_drop, q_lo)   # [B,S,H,D] contiguous
+        ctx.save_for_backward(qkv, o_bshd, lse, kv, rng, q_lo, k_hi)
         ctx.geom = (H, Hk, D, scale, site, p_drop)
         return o_bshd.view(B, S, H * D)
 
     @staticmethod
     def backward(ctx, do):
         m = require_ext()
-        qkv, o_bshd, lse, kv, rng = ctx.saved_tensors
+        qkv, o_bshd, lse, kv, rng, q_lo, k_hi = ctx.saved_tensors
         H, Hk, D, scale, site, p_drop = ctx.geom
         B, S, Fdim = qkv.shape
         q, k, v = _qkv_views(qkv, H, Hk, D)
@@ -684,31 +761,35 @@ class _QKVAttnFn(torch.autograd.Function):
         dqkv = torch.empty_like(qkv)
         m.attn_bwd_packed(do4, q, k, v, o_bshd, lse, scale,
                           *_qkv_views(dqkv, H, Hk, D, bshd=True),
-                          kv, rng, site, p_drop)
-        return dqkv, None, None, None, None, None, None
+                          kv, rng, site, p_drop, q_lo, k_hi)
+        return dqkv, None, None, None, None, None, None, None, None
 
 
 def qkv_attention(qkv: torch.Tensor, n_head: int,
                   n_kv_head: Optional[int] = None,
                   scale: Optional[float] = None,
                   kvlen: Optional[torch.Tensor] = None,
-                  p_drop: float = 0.0, site: int = 0) -> torch.Tensor:
+                  p_drop: float = 0.0, site: int = 0,
+                  q_lo: Optional[torch.Tensor] = None,
+                  k_hi: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Causal attention over a packed qkv projection [B,S,(H+2Hk)·D] →
-    [B,S,H·D]. GQA when n_kv_head < n_head. kvlen/p_drop/site as in
-    :func:`causal_attention`."""
+    [B,S,H·D]. GQA when n_kv_head < n_head. kvlen/p_drop/site/q_lo/k_hi as
+    in :func:`causal_attention`."""
     Hk = n_kv_head or n_head
     B, S, Fdim = qkv.shape
     D = Fdim // (n_head + 2 * Hk)
     if scale is None:
         scale = 1.0 / math.sqrt(D)
     if use_hip(qkv):
-        return _QKVAttnFn.apply(qkv, n_head, Hk, scale, kvlen, p_drop, site)
+        q_lo, k_hi = _doc_bounds(q_lo, k_hi, qkv)
+        return _QKVAttnFn.apply(qkv, n_head, Hk, scale, kvlen, p_drop, site,
+                                q_lo, k_hi)
     E = n_head * D
     kvd = Hk * D
     q = qkv[..., :E].view(B, S, n_head, D).transpose(1, 2)
     k = qkv[..., E:E + kvd].view(B, S, Hk, D).transpose(1, 2)
     v = qkv[..., E + kvd:].view(B, S, Hk, D).transpose(1, 2)
-    o = causal_attention(q, k, v, scale, kvlen, p_drop, site)
+    o = causal_attention(q, k, v, scale, kvlen, p_drop, site, q_lo, k_hi)
     return o.transpose(1, 2).reshape(B, S, E)
 
 
@@ -1043,43 +1124,67 @@ def lm_head_loss(x: torch.Tensor, w: torch.Tensor, targets: torch.Tensor,
 # --------------------------------------------------------------------------
 class _EmbeddingFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, ids, wte, wpe):
+    def forward(ctx, ids, wte, wpe, doc_start=None):
         m = require_ext()
         ids = ids.contiguous()
-        ctx.save_for_backward(ids)
+        ctx.save_for_backward(ids, doc_start)
         ctx.vocab, ctx.npos = wte.shape[0], (wpe.shape[0] if wpe is not None else 0)
         ctx.dim = wte.shape[1]
         ctx.dtype = wte.dtype
         ctx.wteg = getattr(wte, "main_grad", None)
         ctx.wpeg = (getattr(wpe, "main_grad", None)
                     if wpe is not None else None)
-        return m.embedding_fwd(ids, wte, wpe if wpe is not None else torch.empty(0, dtype=wte.dtype, device=wte.device), torch.empty(0, dtype=torch.int32, device=wte.device))
+        return m.embedding_fwd(ids, wte, wpe if wpe is not None else torch.empty(0, dtype=wte.dtype, device=wte.device), torch.empty(0, dtype=torch.int32, device=wte.device), doc_start)
 
     @staticmethod
     def backward(ctx, dy):
         m = require_ext()
-        (ids,) = ctx.saved_tensors
+        ids, doc_start = ctx.saved_tensors
         dwte32, dwpe32 = m.embedding_bwd(dy.contiguous(), ids, ctx.vocab,
-                                         ctx.npos)
+                                         ctx.npos, doc_start)
         dwte = _grad_out(dwte32, ctx.wteg, ctx.dtype)
         dwpe = (_grad_out(dwpe32, ctx.wpeg, ctx.dtype) if ctx.npos
                 else None)
-        return None, dwte, dwpe
+        return None, dwte, dwpe, None
 
 
 def embedding_fwd(ids: torch.Tensor, wte: torch.Tensor,
                   wpe: Optional[torch.Tensor] = None,
-                  pos: Optional[torch.Tensor] = None) -> torch.Tensor:
+                  pos: Optional[torch.Tensor] = None,
+                  doc_start: Optional[torch.Tensor] = None) -> torch.Tensor:
     """x[b,s,:] = wte[ids[b,s]] (+ wpe[pos + s] if given). ``pos``: int32
-    [1] DEVICE offset — graph-replayable decode (inference-only path)."""
+    [1] DEVICE offset — graph-replayable decode (inference-only path).
+    ``doc_start`` (int32, ids-shaped; packed sequences, the attention
+    q_lo): positions restart per document, wpe[s - doc_start[b,s]]. Not
+    combined with ``pos``. It must be a DOCUMENT LAYOUT, which is more than
+    the q_lo contract: every value is the index of a column that starts a
+    document, doc_start[b, doc_start[b,s]] == doc_start[b,s] (what
+    ``packed_text_batches`` produces; :func:`check_doc_start` checks it on
+    the host). The GPU backward finds the documents as the columns with
+    doc_start[b,s] == s; for a q_lo that is no document layout (a sliding
+    window) its dwpe would not be the gradient of the forward."""
+    if doc_start is not None:
+        if pos is not None:
+            raise ValueError("doc_start and pos cannot be combined")
+        if (doc_start.dtype != torch.int32
+                or doc_start.shape != ids.shape):
+            raise ValueError("doc_start must be int32 and shaped like ids")
+        if wpe is None:
+            doc_start = None   # no position table: nothing restarts
     if use_hip(wte):
         if pos is not None:   # serving decode: no autograd needed
             return require_ext().embedding_fwd(
                 ids.contiguous(), wte,
                 wpe if wpe is not None else torch.empty(
                     0, dtype=wte.dtype, device=wte.device), pos)
-        return _EmbeddingFn.apply(ids, wte, wpe)
+        return _EmbeddingFn.apply(
+            ids, wte, wpe,
+            doc_start.contiguous() if doc_start is not None else None)
     x = F.embedding(ids, wte)
+    if doc_start is not None:
+        check_doc_start(doc_start.view(-1, ids.shape[-1]))
+        posn = torch.arange(ids.shape[-1], device=ids.device) - doc_start.long()
+        return x + wpe[posn]
     if wpe is not None:
         off = int(pos.item()) if pos is not None else 0
         x = x + wpe[off:off + ids.shape[-1]].unsqueeze(0)

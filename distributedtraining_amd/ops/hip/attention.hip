@@ -30,6 +30,13 @@
 //   * swapped QK^T: mfma(A=K_tile, B=Q^T) puts a query's scores in lanes
 //     sharing (lane&15) so the softmax row-reduce is two shfl_xor ops;
 //     exp via the single-instruction exp2 path.
+//   * Document mask (packed sequences, DOC instantiations): geo.q_lo adds
+//     the lower bound q_lo[b,q] <= k to the rule. Tile skipping stays
+//     block-uniform: fwd/dq start the key walk at the 32-tile holding q_lo
+//     of the block's first row (the smallest, q_lo is non-decreasing), dkv
+//     ends the query walk at k_hi of the block's last live key. A skipped
+//     tile is one whose probabilities are all exactly 0, so skipping
+//     changes no bit. The unmasked instantiations are the code they were.
 //   * One copy each of the mask rule (attn_visible), the dropout draw of a
 //     32-key tile (attn_drop_hashes/attn_drop_apply) and the accumulator
 //     walk (for_acc_rows); the host gold mirrors them in ops/droprng.py.
@@ -55,6 +62,7 @@ struct AttnCtx {
   const ushort *q, *k, *v, *dout;   // (b, h | hk) base pointers
   float sc2;                        // scale folded into the exp2 argument
   int kvl;                          // keys >= kvl are padding (block-uniform)
+  const int *q_lo, *k_hi;           // document mask rows of b, or null
   uint32_t thr;                     // dropout threshold, 0 = off
   uint64_t drop_s2;                 // per-head dropout seed
 };
@@ -77,6 +85,8 @@ DEV AttnCtx attn_ctx(const AttnGeom& geo, const ushort* q, const ushort* k,
   c.dout = dout + c.b * geo.dout.batch + c.h * geo.dout.head;
   c.sc2 = geo.scale * LOG2E;
   c.kvl = geo.kvlen ? min(geo.seq, geo.kvlen[c.b]) : geo.seq;
+  c.q_lo = geo.q_lo ? geo.q_lo + int64_t(c.b) * geo.seq : nullptr;
+  c.k_hi = geo.k_hi ? geo.k_hi + int64_t(c.b) * geo.seq : nullptr;
   c.thr = geo.drop.thr16;
   c.drop_s2 = 0;
   if (c.thr)
@@ -85,13 +95,28 @@ DEV AttnCtx attn_ctx(const AttnGeom& geo, const ushort* q, const ushort* k,
   return c;
 }
 
-// key k is visible to query q: causal, and not padding of this batch row
-DEV bool attn_visible(int q, int k, int kvl) { return k <= q && k < kvl; }
-
 // Rows past seq are loaded from the last row instead: garbage, but in
 // bounds, and safe everywhere because the matching score/probability lanes
 // are masked to 0.
 DEV int clamp_row(int row, int seq) { return row < seq ? row : seq - 1; }
+
+// key k is visible to query q: causal, not padding of this batch row, and
+// (DOC) not before lo = q_lo[b,q], the start of q's document
+template <bool DOC>
+DEV bool attn_visible(int q, int k, int kvl, int lo) {
+  return (!DOC || lo <= k) && k <= q && k < kvl;
+}
+// The document-mask operands as the kernels read them: row index clamped
+// into the table, value clamped to the contract's range, so no input can
+// move a loop bound or a mask outside [0, seq].
+DEV int doc_lo(const AttnCtx& c, int q, int seq) {
+  q = clamp_row(q, seq);
+  return min(max(c.q_lo[q], 0), q);
+}
+DEV int doc_hi(const AttnCtx& c, int k, int seq) {
+  return min(max(c.k_hi[clamp_row(max(k, 0), seq)], 0), seq);
+}
+
 
 // ---- dropout of a 32-key score tile (fwd, dq) -------------------------------
 // A lane holds keys kv0 + 4g + r and kv0 + 16 + 4g + r (r = 0..3) of query
@@ -207,7 +232,7 @@ DEV void store_acc_tile(ushort* dst, int64_t rstride, int row0, int seq,
 // ---------------- forward ----------------
 // K (row-major) and V (transposed) tiles are staged once per block per
 // 32-key iteration.
-template <int DTILES>  // D = 16*DTILES
+template <int DTILES, bool DOC>  // D = 16*DTILES
 __global__ void attn_fwd_k(const ushort* __restrict__ q,
                            const ushort* __restrict__ k,
                            const ushort* __restrict__ v,
@@ -236,7 +261,11 @@ __global__ void attn_fwd_k(const ushort* __restrict__ q,
   const int blk_kv_end =
       min(min(seq, int(blockIdx.x) * 64 + 64), (kvl + 31) & ~31);  // uniform
   const int my_kv_end = live ? min(seq, q0 + 16) : 0;
-  for (int kv0 = 0; kv0 < blk_kv_end; kv0 += 32) {
+  // DOC: no row of the block sees a key before q_lo of its first row
+  const int lo_q = DOC ? doc_lo(c, qrow, seq) : 0;
+  const int blk_kv_begin =
+      DOC ? (doc_lo(c, int(blockIdx.x) * 64, seq) & ~31) : 0;  // uniform
+  for (int kv0 = blk_kv_begin; kv0 < blk_kv_end; kv0 += 32) {
     __syncthreads();   // previous iteration's LDS reads complete
     stage_tile<DTILES, false>(k_rm, c.k, geo.k.seq, kv0, seq, c.tid);
     stage_tile<DTILES, true>(v_t, c.v, geo.v.seq, kv0, seq, c.tid);
@@ -255,8 +284,10 @@ __global__ void attn_fwd_k(const ushort* __restrict__ q,
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int k0a = kv0 + 4 * g + r, k1a = k0a + 16;
-      p0[r] = attn_visible(qrow, k0a, kvl) ? p0[r] * c.sc2 : -INFINITY;
-      p1[r] = attn_visible(qrow, k1a, kvl) ? p1[r] * c.sc2 : -INFINITY;
+      p0[r] = attn_visible<DOC>(qrow, k0a, kvl, lo_q) ? p0[r] * c.sc2
+                                                      : -INFINITY;
+      p1[r] = attn_visible<DOC>(qrow, k1a, kvl, lo_q) ? p1[r] * c.sc2
+                                                      : -INFINITY;
       mx = fmaxf(mx, fmaxf(p0[r], p1[r]));
     }
     mx = fmaxf(mx, __shfl_xor(mx, 16));
@@ -319,7 +350,7 @@ __global__ void attn_fwd_k(const ushort* __restrict__ q,
 // Also COMPUTES delta[q] = rowsum(dO[q]*O[q]) from its own rows (it loads
 // dO anyway; O rows are one extra coalesced read) and publishes it for the
 // dkv kernel — the standalone delta kernel is gone.
-template <int DTILES>
+template <int DTILES, bool DOC>
 __global__ void attn_bwd_dq_k(const ushort* __restrict__ dout,
                               const ushort* __restrict__ q,
                               const ushort* __restrict__ k,
@@ -366,7 +397,10 @@ __global__ void attn_bwd_dq_k(const ushort* __restrict__ dout,
   const int blk_kv_end =
       min(min(seq, int(blockIdx.x) * 64 + 64), (kvl + 31) & ~31);  // uniform
   const int my_kv_end = live ? min(seq, q0 + 16) : 0;
-  for (int kv0 = 0; kv0 < blk_kv_end; kv0 += 32) {
+  const int lo_q = DOC ? doc_lo(c, qrow, seq) : 0;
+  const int blk_kv_begin =
+      DOC ? (doc_lo(c, int(blockIdx.x) * 64, seq) & ~31) : 0;  // uniform
+  for (int kv0 = blk_kv_begin; kv0 < blk_kv_end; kv0 += 32) {
     __syncthreads();
     stage_tile<DTILES, false>(k_rm, c.k, geo.k.seq, kv0, seq, c.tid);
     stage_tile<DTILES, false>(v_rm, c.v, geo.v.seq, kv0, seq, c.tid);
@@ -400,9 +434,9 @@ __global__ void attn_bwd_dq_k(const ushort* __restrict__ dout,
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int k0a = kv0 + 4 * g + r, k1a = k0a + 16;
-      const float P0 = attn_visible(qrow, k0a, kvl)
+      const float P0 = attn_visible<DOC>(qrow, k0a, kvl, lo_q)
                            ? __builtin_exp2f(s0[r] * c.sc2 - lse_q) : 0.f;
-      const float P1 = attn_visible(qrow, k1a, kvl)
+      const float P1 = attn_visible<DOC>(qrow, k1a, kvl, lo_q)
                            ? __builtin_exp2f(s1[r] * c.sc2 - lse_q) : 0.f;
       s0[r] = P0 * (dp0[r] - dlt_q);
       s1[r] = P1 * (dp1[r] - dlt_q);
@@ -427,7 +461,7 @@ __global__ void attn_bwd_dq_k(const ushort* __restrict__ dout,
 // covers B*H) and results are accumulated with fp32 atomics into dk/dv.
 // Early waves see a few below-diagonal query tiles (probabilities masked
 // to 0) — the price of a uniform, barrier-safe loop.
-template <int DTILES, bool ATOMIC>
+template <int DTILES, bool ATOMIC, bool DOC>
 __global__ void attn_bwd_dkv_k(const ushort* __restrict__ dout,
                                const ushort* __restrict__ q,
                                const ushort* __restrict__ k,
@@ -468,7 +502,13 @@ __global__ void attn_bwd_dkv_k(const ushort* __restrict__ dout,
   // whole walk (uniform) and fall through to the zero-initialized stores
   const int q_start =
       (int(blockIdx.x) * 64 >= kvl) ? seq : int(blockIdx.x) * 64;
-  for (int q0 = q_start; q0 < seq; q0 += 32) {
+  // DOC: no query from k_hi of the block's last live key on sees any key of
+  // the block (k_hi is non-decreasing); uniform, rounded up to the tile
+  const int q_end =
+      DOC ? min(seq, (doc_hi(c, min(int(blockIdx.x) * 64 + 64, kvl) - 1, seq)
+                      + 31) & ~31)
+          : seq;
+  for (int q0 = q_start; q0 < q_end; q0 += 32) {
     __syncthreads();
     stage_tile<DTILES, false>(q_rm, c.q, geo.q.seq, q0, seq, c.tid);
     stage_tile<DTILES, false>(d_rm, c.dout, geo.dout.seq, q0, seq, c.tid);
@@ -495,8 +535,10 @@ __global__ void attn_bwd_dkv_k(const ushort* __restrict__ dout,
     for (int r = 0; r < 4; ++r) {
       // roles swapped: this lane's key krow against the tile's queries
       const int qa0 = q0 + 4 * g + r, qa1 = qa0 + 16;
-      const bool v0 = qa0 < seq && attn_visible(qa0, krow, kvl);
-      const bool v1 = qa1 < seq && attn_visible(qa1, krow, kvl);
+      const bool v0 = qa0 < seq &&
+          attn_visible<DOC>(qa0, krow, kvl, DOC ? doc_lo(c, qa0, seq) : 0);
+      const bool v1 = qa1 < seq &&
+          attn_visible<DOC>(qa1, krow, kvl, DOC ? doc_lo(c, qa1, seq) : 0);
       const float l0 = lse[c.bhid * seq + (v0 ? qa0 : 0)] * LOG2E;
       const float l1 = lse[c.bhid * seq + (v1 ? qa1 : 0)] * LOG2E;
       p0[r] = v0 ? __builtin_exp2f(s0[r] * c.sc2 - l0) : 0.f;
@@ -579,7 +621,7 @@ DEV bf16x8 load_frag_head(const ushort* rm2, int row, int c0) {
                               row & 31, c0);
 }
 
-template <int DTILES>
+template <int DTILES, bool DOC>
 __global__ void attn_bwd_fused_k(const ushort* __restrict__ dout,
                                  const ushort* __restrict__ q,
                                  const ushort* __restrict__ k,
@@ -602,6 +644,9 @@ __global__ void attn_bwd_fused_k(const ushort* __restrict__ dout,
   __shared__ __attribute__((aligned(16))) ushort d_rm[2 * RM];
   __shared__ __attribute__((aligned(16))) ushort pool[4 * RM + 2 * TP];
   __shared__ float lse_s[64], dlt_s[64];
+  // DOC: the head's 64 clamped q_lo values, read per (query, key) pair in
+  // both phases; never referenced (and so not allocated) without DOC
+  __shared__ int lo_s[64];
   ushort* k_rm = pool;
   ushort* v_rm = pool + 2 * RM;
   ushort* k_t = pool + 4 * RM;
@@ -616,6 +661,8 @@ __global__ void attn_bwd_fused_k(const ushort* __restrict__ dout,
     orow[sl] = load_frag_row(op, geo.o.seq, clamp_row(row, seq),
                              32 * sl + 8 * g);
   if (c.tid < 64) lse_s[c.tid] = lse[c.bhid * seq + clamp_row(c.tid, seq)];
+  if constexpr (DOC)
+    if (c.tid < 64) lo_s[c.tid] = doc_lo(c, c.tid, seq);
 #pragma unroll
   for (int t2 = 0; t2 < 2; ++t2) {
     stage_tile<DTILES, false>(q_rm + t2 * RM, c.q, geo.q.seq, 32 * t2, seq,
@@ -652,6 +699,7 @@ __global__ void attn_bwd_fused_k(const ushort* __restrict__ dout,
     const float dlt_q = dpart;
     if (lane < 16 && qrow < seq) dlt_s[qrow] = dlt_q;
     const float lse_q = lse_s[qrow] * LOG2E;  // exp2 units
+    const int lo_q = DOC ? lo_s[qrow] : 0;
     __syncthreads();   // K t (and delta, for the dkv phase) visible
 
     f32x4 acc[DTILES];
@@ -689,9 +737,9 @@ __global__ void attn_bwd_fused_k(const ushort* __restrict__ dout,
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int k0a = kv0 + 4 * g + r, k1a = k0a + 16;
-        const float P0 = attn_visible(qrow, k0a, kvl)
+        const float P0 = attn_visible<DOC>(qrow, k0a, kvl, lo_q)
                              ? __builtin_exp2f(s0[r] * c.sc2 - lse_q) : 0.f;
-        const float P1 = attn_visible(qrow, k1a, kvl)
+        const float P1 = attn_visible<DOC>(qrow, k1a, kvl, lo_q)
                              ? __builtin_exp2f(s1[r] * c.sc2 - lse_q) : 0.f;
         s0[r] = P0 * (dp0[r] - dlt_q);
         s1[r] = P1 * (dp1[r] - dlt_q);
@@ -758,8 +806,10 @@ __global__ void attn_bwd_fused_k(const ushort* __restrict__ dout,
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int qa0 = q0 + 4 * g + r, qa1 = qa0 + 16;
-      const bool v0 = qa0 < seq && attn_visible(qa0, krow, kvl);
-      const bool v1 = qa1 < seq && attn_visible(qa1, krow, kvl);
+      const bool v0 = qa0 < seq &&
+          attn_visible<DOC>(qa0, krow, kvl, DOC ? lo_s[qa0] : 0);
+      const bool v1 = qa1 < seq &&
+          attn_visible<DOC>(qa1, krow, kvl, DOC ? lo_s[qa1] : 0);
       const float l0 = lse_s[v0 ? qa0 : 0] * LOG2E;
       const float l1 = lse_s[v1 ? qa1 : 0] * LOG2E;
       p0[r] = v0 ? __builtin_exp2f(s0[r] * c.sc2 - l0) : 0.f;
@@ -999,6 +1049,13 @@ void for_head_dim(int hd, F f) {
     if (hd == 32) f(std::integral_constant<int, 2>{});
 }
 
+// f(std::bool_constant<DOC>): the document-mask instantiation iff q_lo is set
+template <class F>
+void for_doc_mask(const AttnGeom& geo, F f) {
+  if (geo.q_lo) f(std::true_type{});
+  else f(std::false_type{});
+}
+
 dim3 attn_grid(const AttnGeom& geo) {
   return dim3((geo.seq + 63) / 64, int64_t(geo.B) * geo.H);
 }
@@ -1009,7 +1066,10 @@ void launch_attn_fwd(const bf16_t* q, const bf16_t* k, const bf16_t* v,
                      bf16_t* o, float* lse, const AttnGeom& geo,
                      hipStream_t s) {
   for_head_dim(geo.hd, [&](auto dt) {
-    attn_fwd_k<dt()><<<attn_grid(geo), 256, 0, s>>>(q, k, v, o, lse, geo);
+    for_doc_mask(geo, [&](auto doc) {
+      attn_fwd_k<dt(), doc()><<<attn_grid(geo), 256, 0, s>>>(q, k, v, o, lse,
+                                                             geo);
+    });
   });
 }
 
@@ -1018,8 +1078,10 @@ void launch_attn_bwd_dq(const bf16_t* dout, const bf16_t* q, const bf16_t* k,
                         float* delta, bf16_t* dq, const AttnGeom& geo,
                         hipStream_t s) {
   for_head_dim(geo.hd, [&](auto dt) {
-    attn_bwd_dq_k<dt()><<<attn_grid(geo), 256, 0, s>>>(dout, q, k, v, o, lse,
-                                                       delta, dq, geo);
+    for_doc_mask(geo, [&](auto doc) {
+      attn_bwd_dq_k<dt(), doc()><<<attn_grid(geo), 256, 0, s>>>(
+          dout, q, k, v, o, lse, delta, dq, geo);
+    });
   });
 }
 
@@ -1030,10 +1092,12 @@ void launch_attn_bwd_dkv(const bf16_t* dout, const bf16_t* q,
                          hipStream_t s) {
   for_head_dim(geo.hd, [&](auto dt) {
     // GQA folds heads via fp32 atomics; grp==1 stores bf16 directly
-    auto kern = geo.grp > 1 ? attn_bwd_dkv_k<dt(), true>
-                            : attn_bwd_dkv_k<dt(), false>;
-    kern<<<attn_grid(geo), 256, 0, s>>>(dout, q, k, v, lse, delta, dk32,
-                                        dv32, dk, dv, geo);
+    for_doc_mask(geo, [&](auto doc) {
+      auto kern = geo.grp > 1 ? attn_bwd_dkv_k<dt(), true, doc()>
+                              : attn_bwd_dkv_k<dt(), false, doc()>;
+      kern<<<attn_grid(geo), 256, 0, s>>>(dout, q, k, v, lse, delta, dk32,
+                                          dv32, dk, dv, geo);
+    });
   });
 }
 
@@ -1043,12 +1107,14 @@ void launch_attn_bwd_fused(const bf16_t* dout, const bf16_t* q,
                            bf16_t* dv, const AttnGeom& geo, hipStream_t s) {
   // dta_attn_bwd_fused_shape(geo) holds: one 64-row tile, hd 32 or 64
   const dim3 grid(1, int64_t(geo.B) * geo.H);
-  if (geo.hd == 64)
-    attn_bwd_fused_k<4><<<grid, 256, 0, s>>>(dout, q, k, v, o, lse, dq, dk,
-                                             dv, geo);
-  else
-    attn_bwd_fused_k<2><<<grid, 256, 0, s>>>(dout, q, k, v, o, lse, dq, dk,
-                                             dv, geo);
+  for_doc_mask(geo, [&](auto doc) {
+    if (geo.hd == 64)
+      attn_bwd_fused_k<4, doc()><<<grid, 256, 0, s>>>(dout, q, k, v, o, lse,
+                                                      dq, dk, dv, geo);
+    else
+      attn_bwd_fused_k<2, doc()><<<grid, 256, 0, s>>>(dout, q, k, v, o, lse,
+                                                      dq, dk, dv, geo);
+  });
 }
 
 void launch_mfma_probe_16(const bf16_t* A, const bf16_t* B, float* D,

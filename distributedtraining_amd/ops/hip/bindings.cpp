@@ -812,8 +812,23 @@ std::vector<Tensor> ce_fwd_bwd(Tensor logits, Tensor targets,
 }
 
 // ---- embedding -------------------------------------------------------------
-// pos: optional int32 [1] device offset for the wpe row (graph decode)
-Tensor embedding_fwd(Tensor ids, Tensor wte, Tensor wpe, Tensor pos) {
+// Document layout of packed sequences (the attention q_lo, the embedding's
+// doc_start): int32, contiguous, on the GPU, the shape given. The values
+// are not read here (that would sync): the kernels clamp them.
+const int* doc_table(const c10::optional<Tensor>& t, at::IntArrayRef shape,
+                     const char* name) {
+  if (!t.has_value() || !t->defined() || t->numel() == 0) return nullptr;
+  TORCH_CHECK(t->is_cuda() && t->scalar_type() == torch::kInt32 &&
+                  t->is_contiguous() && t->sizes() == shape,
+              name, " must be a contiguous int32 GPU tensor of shape ", shape);
+  return t->data_ptr<int>();
+}
+
+// pos: optional int32 [1] device offset for the wpe row (graph decode).
+// doc_start: optional int32 ids-shaped tensor; the position restarts at
+// every document start (wpe row s - doc_start[b, s]).
+Tensor embedding_fwd(Tensor ids, Tensor wte, Tensor wpe, Tensor pos,
+                     c10::optional<Tensor> doc_start) {
   check_bf16(wte, "wte");
   TORCH_CHECK(ids.scalar_type() == torch::kInt64, "ids int64");
   const bool has_wpe = wpe.numel() > 0;
@@ -829,9 +844,13 @@ Tensor embedding_fwd(Tensor ids, Tensor wte, Tensor wpe, Tensor pos) {
                 "pos must be an int32 GPU scalar");
     posp = pos.data_ptr<int>();
   }
+  const int* dsp = doc_table(doc_start, ids.sizes(), "doc_start");
+  if (dsp && has_wpe)
+    TORCH_CHECK(ids.is_contiguous() && seq <= wpe.size(0),
+                "doc_start needs contiguous ids and seq <= wpe rows");
   launch_embedding_fwd(ids.data_ptr<int64_t>(), bfp(wte),
                        has_wpe ? bfp(wpe) : nullptr, bfp_mut(out), n_tok,
-                       seq, dim, has_wpe, posp, stream());
+                       seq, dim, has_wpe, posp, dsp, stream());
   return out;
 }
 
@@ -872,7 +891,8 @@ void i32_inc(Tensor t) {
 }
 
 std::vector<Tensor> embedding_bwd(Tensor dy, Tensor ids, int64_t vocab,
-                                  int64_t npos) {
+                                  int64_t npos,
+                                  c10::optional<Tensor> doc_start) {
   check_bf16(dy, "dy");
   const int dim = int(dy.size(-1));
   const int seq = int(ids.size(-1));
@@ -883,7 +903,19 @@ std::vector<Tensor> embedding_bwd(Tensor dy, Tensor ids, int64_t vocab,
   launch_embedding_bwd(bfp(dy), ids.data_ptr<int64_t>(),
                        dwte.data_ptr<float>(), nullptr, n_tok, seq, dim,
                        false, stream());
-  if (npos) {
+  const int* dsp = doc_table(doc_start, ids.sizes(), "doc_start");
+  if (npos && dsp) {
+    // positions restart per document: dwpe[p,:] sums the tokens at offset p
+    // of their document (two-phase like the column sum, no atomics)
+    const int64_t B = n_tok / seq;
+    TORCH_CHECK(dim % 8 == 0 && seq <= npos && ids.is_contiguous(),
+                "doc_start: dim % 8 == 0, seq <= npos, contiguous ids");
+    const int stripes = dta_doc_dwpe_stripes(B, seq, dim);
+    auto part = torch::empty({stripes, int64_t(seq) * dim}, f32);
+    launch_embedding_dwpe_doc(bfp(dy), dsp, part.data_ptr<float>(),
+                              dwpe.data_ptr<float>(), B, seq, dim, stripes,
+                              stream());
+  } else if (npos) {
     // dwpe[s,:] = sum_b dy[b,s,:] — batch-dim column reduction over the
     // [B, seq*dim] view (B-way same-address atomics measured dominant in
     // the scatter version)
@@ -962,8 +994,18 @@ static void check_attn_view(const Tensor& t, const char* n) {
 // kvlen: int32 [B] valid-key prefix per batch row (empty = no mask);
 // rng: int64 [1] device step counter + site/p: attention-prob dropout
 // (p == 0 disables).
+// q_lo / k_hi: optional int32 [B,S] document mask (dta_kernels.h AttnGeom).
+using OptDoc = c10::optional<Tensor>;
 static void set_mask_drop(AttnGeom& g, const Tensor& kvlen, const Tensor& rng,
-                          int64_t site, double p, int64_t B) {
+                          int64_t site, double p, int64_t B,
+                          const OptDoc& q_lo = c10::nullopt,
+                          const OptDoc& k_hi = c10::nullopt,
+                          bool need_k_hi = false) {
+  g.q_lo = doc_table(q_lo, {B, int64_t(g.seq)}, "q_lo");
+  g.k_hi = doc_table(k_hi, {B, int64_t(g.seq)}, "k_hi");
+  TORCH_CHECK(!(need_k_hi && g.q_lo) || g.k_hi,
+              "the backward needs k_hi whenever q_lo is given");
+  if (!g.q_lo) g.k_hi = nullptr;
   if (kvlen.numel() > 0) {
     TORCH_CHECK(kvlen.scalar_type() == torch::kInt32 && kvlen.is_cuda() &&
                     kvlen.is_contiguous() && kvlen.numel() == B,
@@ -1001,7 +1043,7 @@ static AttnGeom make_geom(const Tensor& q, const Tensor& k, const Tensor& v,
 
 std::vector<Tensor> attn_fwd(Tensor q, Tensor k, Tensor v, double scale,
                              Tensor kvlen, Tensor rng, int64_t site,
-                             double p) {
+                             double p, OptDoc q_lo) {
   check_attn_view(q, "q"); check_attn_view(k, "k"); check_attn_view(v, "v");
   const int hd = int(q.size(3));
   TORCH_CHECK(hd == 32 || hd == 64 || hd == 128, "head dim must be 32/64/128");
@@ -1009,7 +1051,7 @@ std::vector<Tensor> attn_fwd(Tensor q, Tensor k, Tensor v, double scale,
   auto o = torch::empty({B, S, H, hd}, q.options());
   auto lse = torch::empty({B * H, S}, q.options().dtype(torch::kFloat32));
   AttnGeom geo = make_geom(q, k, v, o, Tensor(), scale);
-  set_mask_drop(geo, kvlen, rng, site, p, B);
+  set_mask_drop(geo, kvlen, rng, site, p, B, q_lo);
   launch_attn_fwd(bfp(q), bfp(k), bfp(v), bfp_mut(o),
                   lse.data_ptr<float>(), geo, stream());
   return {o, lse};  // caller views o as [B,H,S,D] via permute(0,2,1,3)
@@ -1043,13 +1085,14 @@ static std::pair<Tensor, Tensor> attn_bwd_into(
     const Tensor& dout, const Tensor& q, const Tensor& k, const Tensor& v,
     const Tensor& o_bshd, const Tensor& lse, double scale,
     const Tensor& kvlen, const Tensor& rng, int64_t site, double p,
-    Tensor dq_v, Tensor dk_v, Tensor dv_v) {
+    Tensor dq_v, Tensor dk_v, Tensor dv_v, const OptDoc& q_lo,
+    const OptDoc& k_hi) {
   check_attn_view(dout, "dout");
   TORCH_CHECK(dq_v.stride(3) == 1, "dq view needs contiguous head_dim");
   const int64_t B = q.size(0), H = q.size(1), S = q.size(2);
   AttnGeom geo = make_geom(q, k, v, o_bshd, dout, scale);
   geo.dq = strides_bshd(dq_v);
-  set_mask_drop(geo, kvlen, rng, site, p, B);
+  set_mask_drop(geo, kvlen, rng, site, p, B, q_lo, k_hi, true);
   if (attn_bwd_fused_on() && dta_attn_bwd_fused_shape(geo)) {
     TORCH_CHECK(dk_v.stride(3) == 1 && dk_v.strides() == dv_v.strides(),
                 "dk/dv views need contiguous head_dim and equal strides");
@@ -1088,7 +1131,7 @@ static std::pair<Tensor, Tensor> attn_bwd_into(
 std::vector<Tensor> attn_bwd(Tensor dout, Tensor q, Tensor k, Tensor v,
                              Tensor o_bshd, Tensor lse, double scale,
                              Tensor kvlen, Tensor rng, int64_t site,
-                             double p) {
+                             double p, OptDoc q_lo, OptDoc k_hi) {
   const int64_t B = q.size(0), H = q.size(1), S = q.size(2), hd = q.size(3);
   const int64_t Hk = k.size(1);
   auto dq = torch::empty({B, S, H, hd}, q.options());
@@ -1098,7 +1141,7 @@ std::vector<Tensor> attn_bwd(Tensor dout, Tensor q, Tensor k, Tensor v,
     dv = torch::empty_like(dk);
   }
   auto [dk32, dv32] = attn_bwd_into(dout, q, k, v, o_bshd, lse, scale, kvlen,
-                                    rng, site, p, dq, dk, dv);
+                                    rng, site, p, dq, dk, dv, q_lo, k_hi);
   if (H == Hk) return {dq, dk.permute({0, 2, 1, 3}), dv.permute({0, 2, 1, 3})};
   return {dq, dk32.to(torch::kBFloat16), dv32.to(torch::kBFloat16)};
 }
@@ -1109,11 +1152,12 @@ std::vector<Tensor> attn_bwd(Tensor dout, Tensor q, Tensor k, Tensor v,
 void attn_bwd_packed(Tensor dout, Tensor q, Tensor k, Tensor v,
                      Tensor o_bshd, Tensor lse, double scale, Tensor dq_v,
                      Tensor dk_v, Tensor dv_v, Tensor kvlen, Tensor rng,
-                     int64_t site, double p) {
+                     int64_t site, double p, OptDoc q_lo, OptDoc k_hi) {
   TORCH_CHECK(dk_v.stride(3) == 1 && dv_v.stride(3) == 1,
               "dqkv views need contiguous head_dim");
   auto [dk32, dv32] = attn_bwd_into(dout, q, k, v, o_bshd, lse, scale, kvlen,
-                                    rng, site, p, dq_v, dk_v, dv_v);
+                                    rng, site, p, dq_v, dk_v, dv_v, q_lo,
+                                    k_hi);
   if (!dk32.defined()) return;
   dk_v.copy_(dk32.permute({0, 2, 1, 3}));
   dv_v.copy_(dv32.permute({0, 2, 1, 3}));
@@ -1207,16 +1251,28 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("ce_chunk", &ce_chunk);
   m.def("ce_finalize", &ce_finalize);
   m.def("head_loss_fwd", &head_loss_fwd);
-  m.def("embedding_fwd", &embedding_fwd);
-  m.def("embedding_bwd", &embedding_bwd);
+  m.def("embedding_fwd", &embedding_fwd, py::arg("ids"), py::arg("wte"),
+        py::arg("wpe"), py::arg("pos"), py::arg("doc_start") = py::none());
+  m.def("embedding_bwd", &embedding_bwd, py::arg("dy"), py::arg("ids"),
+        py::arg("vocab"), py::arg("npos"),
+        py::arg("doc_start") = py::none());
   m.def("kv_append", &kv_append);
   m.def("i32_inc", &i32_inc);
   m.def("gemv", &gemv);
   m.def("rope_fwd", &rope_fwd);
   m.def("rope_bwd", &rope_bwd);
-  m.def("attn_fwd", &attn_fwd);
-  m.def("attn_bwd", &attn_bwd);
-  m.def("attn_bwd_packed", &attn_bwd_packed);
+  m.def("attn_fwd", &attn_fwd, py::arg("q"), py::arg("k"), py::arg("v"),
+        py::arg("scale"), py::arg("kvlen"), py::arg("rng"), py::arg("site"),
+        py::arg("p"), py::arg("q_lo") = py::none());
+  m.def("attn_bwd", &attn_bwd, py::arg("dout"), py::arg("q"), py::arg("k"),
+        py::arg("v"), py::arg("o_bshd"), py::arg("lse"), py::arg("scale"),
+        py::arg("kvlen"), py::arg("rng"), py::arg("site"), py::arg("p"),
+        py::arg("q_lo") = py::none(), py::arg("k_hi") = py::none());
+  m.def("attn_bwd_packed", &attn_bwd_packed, py::arg("dout"), py::arg("q"),
+        py::arg("k"), py::arg("v"), py::arg("o_bshd"), py::arg("lse"),
+        py::arg("scale"), py::arg("dq_v"), py::arg("dk_v"), py::arg("dv_v"),
+        py::arg("kvlen"), py::arg("rng"), py::arg("site"), py::arg("p"),
+        py::arg("q_lo") = py::none(), py::arg("k_hi") = py::none());
   m.def("attn_bwd_fused_enable", &attn_bwd_fused_enable);
   m.def("attn_bwd_fused_calls", &attn_bwd_fused_calls);
   m.def("attn_decode", &attn_decode);

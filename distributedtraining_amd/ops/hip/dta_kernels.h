@@ -344,11 +344,29 @@ void launch_head_loss(const bf16_t* x, const bf16_t* w,
                       float* m_run, float* s_run, hipStream_t s);
 
 // ---- embedding ------------------------------------------------------------
-// pos_p: device position offset for wpe (graph-replayable decode)
+// pos_p: device position offset for wpe (graph-replayable decode).
+// doc_start: optional int32 [n_tok] (packed sequences, the attention q_lo):
+// the wpe row of token t becomes (t % seq_len) - doc_start[t], with
+// doc_start clamped to [0, t % seq_len].
 void launch_embedding_fwd(const int64_t* ids, const bf16_t* wte,
                           const bf16_t* wpe, bf16_t* out, int64_t n_tok,
                           int seq_len, int dim, bool has_wpe,
-                          const int* pos_p, hipStream_t s);
+                          const int* pos_p, const int* doc_start,
+                          hipStream_t s);
+// dwpe under restarting positions: out[p, :] = sum of dy[b, s, :] over the
+// tokens with s - doc_start[b, s] == p, for p < seq (out: fp32 [seq * dim],
+// stored). A document starts where clamp(doc_start[b, s], 0, s) == s and
+// runs to the next start: doc_start must be a document layout (every value
+// is the index of such a column), which is more than the q_lo contract; for
+// any other tensor this is not the gradient of launch_embedding_fwd. part: [dta_doc_dwpe_stripes(B, seq, dim),
+// seq * dim] fp32; dim % 8 == 0. Reads dy once, no atomics, repeats bit
+// for bit.
+inline int dta_doc_dwpe_stripes(int64_t B, int seq, int dim) {
+  return dta_colred_stripes(B, seq * dim);
+}
+void launch_embedding_dwpe_doc(const bf16_t* dy, const int* doc_start,
+                               float* part, float* out, int64_t B, int seq,
+                               int dim, int stripes, hipStream_t s);
 // KV-cache append at device position *pos_p + device int increment
 void launch_kv_append(const bf16_t* kn, const bf16_t* vn, int64_t knb,
                       bf16_t* kc, bf16_t* vc, const int* pos_p, int B,
@@ -387,6 +405,15 @@ struct AttnGeom {
   const int* kvlen = nullptr;
   // attention-probability dropout (transformers GPT-2 attn_pdrop)
   DropParams drop;
+  // document mask (packed sequences), int32 [B, seq] each, null = none:
+  // key k is visible to query q iff q_lo[b,q] <= k on top of the rules
+  // above. Contract: 0 <= q_lo[b,q] <= q, non-decreasing in q. k_hi[b,k] =
+  // #{q : q_lo[b,q] <= k}, one past the last query that sees key k (the
+  // backward's loop bound; required there whenever q_lo is set). The
+  // kernels clamp what they read to [0, q] and [0, seq]: a tensor that
+  // breaks the contract gives wrong numbers, never an out-of-bounds access.
+  const int* q_lo = nullptr;
+  const int* k_hi = nullptr;
 };
 void launch_attn_fwd(const bf16_t* q, const bf16_t* k, const bf16_t* v,
                      bf16_t* o, float* lse, const AttnGeom& geo,

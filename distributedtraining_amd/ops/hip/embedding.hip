@@ -1,11 +1,14 @@
 // Fused token+position embedding gather (fwd) and scatter-add (bwd).
 // Replaces the reference's transformers wte/wpe lookup.
 // fwd: out[t,:] = wte[ids[t]] + wpe[t % seq]; one wave per token row.
+// Packed sequences (doc_start): the position restarts at every document,
+// wpe[t % seq - doc_start[t]].
 // bwd: dwte = fp32 atomicAdd scatter (random token ids: low contention);
 // dwpe is NOT scattered here — every batch row hits the same seq_len
 // positions (B-way contention per element, measured dominant) — it's a
 // plain batch-dim column reduction handled by launch_colsum in the
-// binding. fp32 accumulate, cast after.
+// binding. fp32 accumulate, cast after. With restarting positions the
+// column sum no longer applies: emb_dwpe_doc_k, same two-phase shape.
 #include "dta_common.h"
 #include "dta_kernels.h"
 
@@ -19,7 +22,8 @@ __global__ void emb_fwd_k(const int64_t* __restrict__ ids,
                           const ushort* __restrict__ wpe,
                           ushort* __restrict__ out, int64_t n_tok,
                           int seq_len, int dim,
-                          const int* __restrict__ pos_p) {
+                          const int* __restrict__ pos_p,
+                          const int* __restrict__ doc_start) {
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const int nchunk = dim >> 3;
   // pos_p: device position offset (graph-replayable decode: wpe row =
@@ -29,8 +33,10 @@ __global__ void emb_fwd_k(const int64_t* __restrict__ ids,
        t += int64_t(gridDim.x) * ROW_WAVES) {
     const int64_t id = ids[t];
     const ushort* te = wte + id * dim;
-    const ushort* pe =
-        HAS_WPE ? wpe + int64_t(pos0 + t % seq_len) * dim : nullptr;
+    int pos = int(t % seq_len);
+    // clamped to [0, pos]: a bad doc_start cannot move the row out of wpe
+    if (HAS_WPE && doc_start) pos -= min(max(doc_start[t], 0), pos);
+    const ushort* pe = HAS_WPE ? wpe + int64_t(pos0 + pos) * dim : nullptr;
     ushort* o = out + t * dim;
     for (int c = lane; c < nchunk; c += 64) {
       s16x8 v = *reinterpret_cast<const s16x8*>(te + c * 8);
@@ -62,6 +68,65 @@ __global__ void emb_bwd_k(const ushort* __restrict__ dy,
       atomicAdd(te + c * 2 + 1, bf2f(g[c * 2 + 1]));
     }
   }
+}
+
+// dwpe with positions that restart per document, phase 1 of 2. Block
+// (x, y) owns 256 output slots (p, 8 columns) and the stripe y of batch
+// rows; lanes run along the columns, so a wave reads contiguous 16 B pieces
+// of one dy row. Per batch row, wave 0 compacts the document starts into
+// LDS in order (ballot + popcount); every thread then adds dy[b, st + p]
+// for each document [st, end) longer than p. Fixed order (b, then document)
+// and one writer per panel element: repeats bit for bit. Every dy element
+// is read by exactly one thread. The trip counts depend on blockIdx only;
+// nothing returns before the last __syncthreads.
+__global__ void emb_dwpe_doc_k(const ushort* __restrict__ dy,
+                               const int* __restrict__ doc_start,
+                               float* __restrict__ part, int64_t B, int seq,
+                               int dim) {
+  extern __shared__ int starts[];   // [seq + 1]: starts, then the end `seq`
+  __shared__ int ndoc_s;
+  const int nchunk = dim >> 3;
+  const int64_t slot = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  const bool own = slot < int64_t(seq) * nchunk;
+  const int p = own ? int(slot / nchunk) : 0;
+  const int c8 = own ? int(slot % nchunk) * 8 : 0;
+  const int lane = threadIdx.x & 63;
+  const int64_t b0 = (B * blockIdx.y) / gridDim.y;
+  const int64_t b1 = (B * (blockIdx.y + 1)) / gridDim.y;
+  float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  for (int64_t b = b0; b < b1; ++b) {
+    __syncthreads();   // previous row's list no longer read
+    if (threadIdx.x < 64) {
+      const int* ds = doc_start + b * seq;
+      int n = 0;
+      for (int s0 = 0; s0 < seq; s0 += 64) {
+        const int s = s0 + lane;
+        const bool st = s < seq && min(max(ds[s < seq ? s : 0], 0), s) == s;
+        const unsigned long long m = __ballot(st);
+        if (st) starts[n + __popcll(m & ((1ull << lane) - 1ull))] = s;
+        n += __popcll(m);
+      }
+      if (lane == 0) {
+        starts[n] = seq;
+        ndoc_s = n;
+      }
+    }
+    __syncthreads();
+    if (!own) continue;   // after the barriers
+    const int ndoc = ndoc_s;
+    const ushort* row = dy + b * int64_t(seq) * dim + c8;
+    for (int d = 0; d < ndoc; ++d) {
+      const int s = starts[d] + p;
+      if (s >= starts[d + 1]) continue;
+      const s16x8 v = *reinterpret_cast<const s16x8*>(row + int64_t(s) * dim);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) acc[j] += bf2f(ushort(v[j]));
+    }
+  }
+  if (!own) return;
+  float* o = part + int64_t(blockIdx.y) * seq * dim + int64_t(p) * dim + c8;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) o[j] = acc[j];
 }
 
 // KV-cache append at a DEVICE position (graph-replayable decode): write
@@ -106,15 +171,28 @@ void launch_i32_inc(int* p, hipStream_t s) { i32_inc_k<<<1, 1, 0, s>>>(p); }
 void launch_embedding_fwd(const int64_t* ids, const bf16_t* wte,
                           const bf16_t* wpe, bf16_t* out, int64_t n_tok,
                           int seq_len, int dim, bool has_wpe,
-                          const int* pos_p, hipStream_t s) {
+                          const int* pos_p, const int* doc_start,
+                          hipStream_t s) {
   int64_t want = (n_tok + ROW_WAVES - 1) / ROW_WAVES;
   const int grid = int(want < 4096 ? (want > 0 ? want : 1) : 4096);
   if (has_wpe)
     emb_fwd_k<true><<<grid, 256, 0, s>>>(ids, wte, wpe, out, n_tok, seq_len,
-                                         dim, pos_p);
+                                         dim, pos_p, doc_start);
   else
     emb_fwd_k<false><<<grid, 256, 0, s>>>(ids, wte, nullptr, out, n_tok,
-                                          seq_len, dim, nullptr);
+                                          seq_len, dim, nullptr, nullptr);
+}
+
+void launch_embedding_dwpe_doc(const bf16_t* dy, const int* doc_start,
+                               float* part, float* out, int64_t B, int seq,
+                               int dim, int stripes, hipStream_t s) {
+  const int cols = seq * dim;
+  const int64_t slots = int64_t(seq) * (dim / 8);
+  dim3 grid(unsigned((slots + 255) / 256), unsigned(stripes));
+  emb_dwpe_doc_k<<<grid, 256, (seq + 1) * sizeof(int), s>>>(dy, doc_start,
+                                                            part, B, seq, dim);
+  launch_colred_finish({part, nullptr, out, nullptr, nullptr, nullptr,
+                        stripes, cols, cols}, s);
 }
 
 void launch_embedding_bwd(const bf16_t* dy, const int64_t* ids,

@@ -51,6 +51,12 @@ class GraphedMinerStep:
         if b0.get("attention_mask") is not None:
             self.mask = b0["attention_mask"].to(dev).clone()
             self._static["attention_mask"] = self.mask
+        # packed sequences: the document layout is a static buffer too, so
+        # every replay reads the layout of the batch it was fed
+        self.doc_start = None
+        if b0.get("doc_start") is not None:
+            self.doc_start = b0["doc_start"].to(dev).clone()
+            self._static["doc_start"] = self.doc_start
 
         # warmup on a side stream (torch requirement before capture)
         s = torch.cuda.Stream()
@@ -83,6 +89,17 @@ class GraphedMinerStep:
                              "re-capture to feed distinct labels")
         if self.mask is not None:
             self.mask.copy_(batch["attention_mask"], non_blocking=True)
+        ds = batch.get("doc_start")
+        if self.doc_start is not None:
+            if ds is None:
+                raise ValueError("graph captured with doc_start; this batch "
+                                 "has none")
+            self.doc_start.copy_(ds, non_blocking=True)
+        elif ds is not None:
+            # the captured kernels are the unmasked ones: the documents of
+            # this batch would silently attend to each other
+            raise ValueError("graph captured without doc_start; re-capture "
+                             "to feed packed batches")
         self.graph.replay()
         self.miner.step_count += 1
         self.miner.total_examples += self.batch_size

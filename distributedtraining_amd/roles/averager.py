@@ -32,6 +32,7 @@ from ..config import AverageConfig
 from ..parallel.flat import FlatParams
 from ..registry import Registry
 from ..store import FileStore
+from ..utils.textdata import doc_start_kw
 
 log = logging.getLogger(__name__)
 
@@ -108,7 +109,8 @@ class ParameterizedAverager:
                 if am is not None:
                     am = am.to(self.fp.device)
                 out = self.model(input_ids=ids, attention_mask=am,
-                                 labels=labels)
+                                 labels=labels,
+                                 **doc_start_kw(batch, self.fp.device))
                 if not bool(torch.isfinite(out.loss)):
                     # a bad delta can make some merge diverge mid-search;
                     # skip the update rather than poisoning W (the
@@ -169,9 +171,10 @@ class ParameterizedAverager:
                     am = batch.get("attention_mask")
                     if am is not None:
                         am = am.to(self.fp.device)
-                    total += float(self.model(input_ids=ids,
-                                              attention_mask=am,
-                                              labels=labels).loss) * ids.shape[0]
+                    total += float(self.model(
+                        input_ids=ids, attention_mask=am, labels=labels,
+                        **doc_start_kw(batch, self.fp.device)
+                    ).loss) * ids.shape[0]
                     cnt += ids.shape[0]
             return -total / max(cnt, 1)  # reference fitness = −val loss (:895-910)
 

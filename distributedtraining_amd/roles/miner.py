@@ -28,6 +28,7 @@ from ..config import TrainConfig
 from ..parallel.flat import FlatParams, FusedAdamW
 from ..registry import Registry
 from ..store import DeltaCheckpoint, FileStore
+from ..utils.textdata import doc_start_kw
 
 log = logging.getLogger(__name__)
 
@@ -112,7 +113,7 @@ class DeltaLoop:
         if am is not None:
             am = am.to(self.fp.device, non_blocking=True)
         out = self.model(input_ids=input_ids, attention_mask=am,
-                         labels=labels)
+                         labels=labels, **doc_start_kw(batch, self.fp.device))
         out.loss.backward()
         self.opt.step()
         self._on_grad_available()   # subclass hook (gradient protocol)

@@ -31,6 +31,7 @@ from ..config import ValidateConfig
 from ..parallel.flat import FlatParams
 from ..registry import Registry
 from ..store import DeltaCheckpoint, FileStore
+from ..utils.textdata import doc_start_kw
 
 log = logging.getLogger(__name__)
 
@@ -67,7 +68,7 @@ class DeltaValidator:
             if am is not None:
                 am = am.to(self.fp.device)
             out = self.model(input_ids=ids, attention_mask=am, labels=labels,
-                             **head_kw)
+                             **head_kw, **doc_start_kw(batch, self.fp.device))
             total_loss += float(out.loss) * ids.shape[0]
             total_samples += ids.shape[0]
         self.model.train()
