@@ -10,6 +10,11 @@ data round over round (the whole point of the reference's protocol).
 
 Usage: python benchmarks/convergence.py [--rounds 6] [--miners 4]
        [--steps-per-round 30] [--strategy mean|nesterov|parameterized]
+       [--exchange-dtype fp32|bf16|int8|topk] [--topk-k 128]
+       [--topk-block 4096] [--topk-error-feedback true|false]
+--exchange-dtype (default fp32: the deltas reach the averager as they are)
+sends every miner's delta through that wire form first; topk keeps one
+error-feedback residual per miner across the rounds.
 Prints one JSON line; add --table for a human round-by-round table.
 """
 
@@ -36,12 +41,20 @@ def main() -> int:
                          "byte-level BPE trained offline on the corpus "
                          "(ragged lengths -> the padding/attention-mask "
                          "path is exercised end to end)")
+    ap.add_argument("--exchange-dtype", default="fp32",
+                    choices=["fp32", "bf16", "int8", "topk"])
+    ap.add_argument("--topk-k", type=int, default=128)
+    ap.add_argument("--topk-block", type=int, default=4096)
+    ap.add_argument("--topk-error-feedback", default="true",
+                    choices=["true", "false"])
     ap.add_argument("--table", action="store_true")
     args = ap.parse_args()
 
     from distributedtraining_amd.config import (AverageConfig, Config,
                                                 ModelConfig)
+    from distributedtraining_amd import ops
     from distributedtraining_amd.models import build_model
+    from distributedtraining_amd.parallel.comm import PackedDeltas
     from distributedtraining_amd.parallel.flat import FlatParams
     from distributedtraining_amd.roles.averager import ParameterizedAverager
     from distributedtraining_amd.roles.miner import DeltaLoop
@@ -92,6 +105,8 @@ def main() -> int:
                                AverageConfig(strategy=args.strategy,
                                              meta_epochs=2, meta_lr=0.01))
     losses = [validator.base_loss]
+    feedback = args.topk_error_feedback == "true"
+    residuals = [None] * args.miners     # topk: what a miner has not sent
 
     for rnd in range(args.rounds):
         deltas = []
@@ -102,8 +117,22 @@ def main() -> int:
                              text_batches(ds, 16, seed=100 * rnd + m),
                              cfg.train)
             loop.train(args.steps_per_round)
-            deltas.append(loop.make_delta().flat.clone())
+            delta = loop.make_delta().flat.clone()
+            if args.exchange_dtype == "topk":
+                if feedback and residuals[m] is None:
+                    residuals[m] = torch.zeros_like(delta)
+                delta, _ = ops.topk_compress_blockwise(
+                    delta, args.topk_k, args.topk_block,
+                    residual=residuals[m], update_residual=feedback)
+            deltas.append(delta)
         stack = torch.stack(deltas)
+        if args.exchange_dtype == "topk":
+            stack = PackedDeltas("topk", stack, fp.numel, None,
+                                 args.topk_block, args.topk_k)
+        elif args.exchange_dtype != "fp32":
+            stack = PackedDeltas.pack(stack, args.exchange_dtype)
+        if args.exchange_dtype != "fp32" and args.strategy == "nesterov":
+            stack = stack.dequantize()
         fp.load_flat_master(base)
         if args.strategy == "parameterized":
             merged = av.meta_learning(base, stack, ev)
@@ -126,11 +155,15 @@ def main() -> int:
            "device": "MI355X" if use_gpu else "cpu",
            "tokenizer": args.tokenizer, "vocab_size": vs,
            "strategy": args.strategy, "miners": args.miners,
+           "exchange_dtype": args.exchange_dtype,
            "steps_per_round": args.steps_per_round,
            "rounds": args.rounds, "initial_loss": round(losses[0], 4),
            "final_loss": round(losses[-1], 4),
            "losses": [round(x, 4) for x in losses],
            "improved": losses[-1] < losses[0]}
+    if args.exchange_dtype == "topk":
+        out.update(topk_k=args.topk_k, topk_block=args.topk_block,
+                   topk_error_feedback=feedback)
     print(json.dumps(out))
     return 0 if out["improved"] else 1
 

@@ -192,9 +192,17 @@ class CommConfig:
     # parameterized strategies need all deltas resident): "fp32" is exact;
     # "bf16" halves the xGMI bytes; "int8" quarters them via blockwise-absmax
     # quantization (worst-case element error absmax(4096-block)/127).
+    # "topk" sends the topk_k largest-magnitude elements of every
+    # topk_block-element block as int32 (index, bf16 value) entries:
+    # ceil(P / topk_block) * topk_k * 4 bytes per delta, P/8 at the defaults
+    # (8x below int8). What is not sent stays in a per-miner fp32 residual
+    # (4P bytes) and is added to the next round's delta (error feedback).
     # mean/nesterov all-reduce stays fp32 always. The wire dtype alone does
     # NOT shrink the resident gather: see resident_dtype.
     exchange_dtype: str = "fp32"
+    topk_k: int = 128            # multiple of 4 in [4, topk_block / 4]
+    topk_block: int = 4096       # power of two in [1024, 16384]
+    topk_error_feedback: bool = True
     # what the gathered deltas look like in HBM. "fp32": the gather is
     # expanded to [world, P] fp32 (world x P x 4 bytes at any wire dtype).
     # "wire": it stays in exchange_dtype form (PackedDeltas) and the merge /

@@ -41,6 +41,7 @@ __all__ = [
     "grad_sumsq_blocks", "grad_sumsq_partials", "step_control",
     "adamw_step_guarded", "lr_schedule",
     "quantize_blockwise_int8", "dequantize_blockwise_int8",
+    "topk_compress_blockwise",
     "dropout", "rng_tick",
 ]
 
@@ -1448,6 +1449,57 @@ def quantize_blockwise_int8(flat: torch.Tensor, block: int = 4096,
     return _q(flat if base is None else flat.float() - base.float(), block)
 
 
+def _plane16(t: torch.Tensor) -> torch.Tensor:
+    """Contiguous and 16 B aligned, as the kernels' vector loads need."""
+    t = t.contiguous()
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+def topk_compress_blockwise(flat: torch.Tensor, k: int = 128,
+                            block: int = 4096,
+                            base: Optional[torch.Tensor] = None,
+                            residual: Optional[torch.Tensor] = None,
+                            update_residual: bool = True):
+    """Blockwise top-k entries of ``d = (flat - base) + residual`` (``base``
+    and ``residual`` optional): ``(entries int32 [nb*k], residual)``.
+
+    The definition is parallel.comm.topk_compress_blockwise (the CPU path);
+    the GPU kernel equals it bit for bit, reads every plane once and never
+    writes ``d``. With ``update_residual`` the fp32 [P] ``residual`` tensor
+    is overwritten in place with the error-feedback remainder and returned
+    (a fresh one is made when ``residual`` is None); without it ``residual``
+    is left untouched and returned as it came."""
+    from ..parallel.comm import check_topk_format, \
+        topk_compress_blockwise as _t
+    check_topk_format(k, block)
+    if residual is not None and (residual.dtype != torch.float32
+                                 or residual.numel() != flat.numel()
+                                 or not residual.is_contiguous()):
+        raise ValueError("residual must be a contiguous fp32 [P] tensor")
+    if use_hip(flat):
+        e = flat.new_empty(0)
+        if residual is not None and residual.data_ptr() % 16 != 0:
+            raise ValueError("residual must be 16-byte aligned")
+        out = e
+        if update_residual:
+            out = residual if residual is not None else torch.empty(
+                flat.numel(), dtype=torch.float32, device=flat.device)
+        # the top-k form of the extension's delta compressor (topk_k > 0)
+        ent, = require_ext().quantize_int8(
+            _plane16(flat), e if base is None else _plane16(base), block,
+            topk_k=k, residual_in=residual,
+            residual_out=out if update_residual else None)
+        return ent, (out if update_residual else residual)
+    d = flat.float() if base is None else flat.float() - base.float()
+    ent, res = _t(d.reshape(-1), k, block, residual)
+    if not update_residual:
+        return ent, residual
+    if residual is not None:
+        residual.copy_(res)
+        res = residual
+    return ent, res
+
+
 def dequantize_blockwise_int8(q: torch.Tensor, scale: torch.Tensor,
                               numel: int, block: int = 4096) -> torch.Tensor:
     """fp32 [numel] of one quantised row: float(q) * scale per block."""
@@ -1464,7 +1516,13 @@ def dequantize_blockwise_int8(q: torch.Tensor, scale: torch.Tensor,
 def axpy_(w: torch.Tensor, x, alpha: float = 1.0) -> torch.Tensor:
     """w += alpha·x (reference delta apply: validation_logic.py:252-259).
     ``x``: a tensor, or ``(PackedDeltas, i)`` for row ``i`` of a packed
-    gather — dequantised in registers, no fp32 copy of the delta."""
+    gather — dequantised in registers, no fp32 copy of the delta.
+
+    A "topk" row is a pure scatter, ``w[e] = fma(alpha, v, w[e])`` over its
+    in-range entries. For finite ``alpha`` that equals the dense kernel on
+    the densified row as numbers; elements off the support are not touched,
+    so a ``-0.0`` in ``w`` that the dense kernel would turn into ``+0.0``
+    may stay ``-0.0``."""
     if isinstance(x, tuple):
         pd, i = x
         if pd.kind == "fp32":
@@ -1487,8 +1545,9 @@ def weighted_merge(base: torch.Tensor, deltas,
     ``W`` is [N, S] per-(miner, parameter-tensor) merge weights; ``offsets``
     [S+1] the flat-buffer segment boundaries. Reference semantics:
     averaging_logic.py:422-470 (get_averaged_params over per-param weights).
-    ``deltas``: [N, P] fp32, or a PackedDeltas (bf16 / int8 stay compressed
-    in memory; the result equals this call on ``deltas.dequantize()``).
+    ``deltas``: [N, P] fp32, or a PackedDeltas (bf16 / int8 / topk stay
+    compressed in memory; the result equals this call on
+    ``deltas.dequantize()``).
     """
     if _packed(deltas) and deltas.kind == "fp32":
         deltas = deltas.data

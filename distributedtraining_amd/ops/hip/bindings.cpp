@@ -573,10 +573,131 @@ void check_plane(const Tensor& t, int64_t P, const char* name) {
   TORCH_CHECK(aligned16(t), name, " must be 16-byte aligned");
 }
 
+// ---- top-k deltas ----------------------------------------------------------
+// The fourth wire form has no export names of its own: the packed entry
+// points below take int32 entries as they take bf16 or int8 data (k is
+// data.size(1) / nb), and quantize_int8 makes them when topk_k > 0.
+bool is_topk(const Tensor& data) {
+  return data.scalar_type() == torch::kInt32;
+}
+// entries per block of int32 [N, nb*k] data; topk_view checks the rest
+int64_t topk_k_of(const Tensor& data, int64_t P, int64_t block) {
+  TORCH_CHECK(data.dim() == 2 && P >= 1 && block >= 1,
+              "topk entries must be [N, nb*k]");
+  return data.size(1) / ((P + block - 1) / block);
+}
+// the format's limits (comm.check_topk_format); returns nb
+int64_t check_topk_format(int64_t P, int64_t k, int64_t block) {
+  TORCH_CHECK(P >= 1, "topk deltas: empty plane");
+  TORCH_CHECK(block >= DTA_TOPK_MIN_BLOCK && block <= DTA_TOPK_MAX_BLOCK &&
+                  (block & (block - 1)) == 0,
+              "topk block must be a power of two in [", DTA_TOPK_MIN_BLOCK,
+              ", ", DTA_TOPK_MAX_BLOCK, "]");
+  TORCH_CHECK(k >= 4 && k % 4 == 0 && k <= block / 4,
+              "topk k must be a multiple of 4 in [4, block / 4]");
+  const int64_t nb = (P + block - 1) / block;
+  TORCH_CHECK(nb < (int64_t(1) << 31), "too many top-k blocks");
+  return nb;
+}
+
+// data: int32 [N, nb*k] entries of N rows of a P-element plane
+TopkView topk_view(const Tensor& data, int64_t P, int64_t k, int64_t block) {
+  const int64_t nb = check_topk_format(P, k, block);
+  TORCH_CHECK(data.is_cuda() && data.dim() == 2 && data.is_contiguous() &&
+                  data.scalar_type() == torch::kInt32,
+              "topk entries must be a contiguous int32 [N, nb*k] GPU tensor");
+  TORCH_CHECK(data.size(0) >= 1 && data.size(0) <= DTA_MERGE_MAX_MODELS,
+              "topk deltas: 1 <= n_models <= ", DTA_MERGE_MAX_MODELS);
+  TORCH_CHECK(data.size(1) == nb * k,
+              "topk entries must be [N, nb*k], nb = ceil(P / block)");
+  TORCH_CHECK(aligned16(data), "topk entries must be 16-byte aligned");
+  int shift = 0;
+  while ((int64_t(1) << shift) < block) ++shift;
+  return TopkView{data.data_ptr<int>(), nb * k, shift, int(k)};
+}
+
+// entries [nb*k] of (x - base) + residual_in; base / residual_in /
+// residual_out empty: not used / not used / not written
+Tensor topk_compress(Tensor x, Tensor base, Tensor residual_in,
+                     Tensor residual_out, int64_t k, int64_t block) {
+  check_f32(x, "x");
+  const int64_t P = x.numel();
+  const int64_t nb = check_topk_format(P, k, block);
+  TORCH_CHECK(aligned16(x), "x must be 16-byte aligned");
+  const float *bp = nullptr, *rin = nullptr;
+  float* rout = nullptr;
+  if (base.numel()) {
+    check_plane(base, P, "base");
+    bp = base.data_ptr<float>();
+  }
+  if (residual_in.numel()) {
+    check_plane(residual_in, P, "residual_in");
+    rin = residual_in.data_ptr<float>();
+  }
+  if (residual_out.numel()) {
+    check_plane(residual_out, P, "residual_out");
+    rout = residual_out.data_ptr<float>();
+  }
+  auto entries = torch::empty({nb * k}, x.options().dtype(torch::kInt32));
+  launch_delta_topk(x.data_ptr<float>(), bp, rin, rout, P, int(block), int(k),
+                    nb, entries.data_ptr<int>(), stream());
+  return entries;
+}
+
+void weighted_merge_topk(Tensor base, Tensor data, int64_t k, int64_t block,
+                         Tensor W, Tensor offsets, Tensor out) {
+  const int64_t P = base.numel();
+  check_plane(base, P, "base"); check_plane(out, P, "out");
+  const TopkView d = topk_view(data, P, k, block);
+  const int n_models = merge_n_models(data.size(0));
+  const int n_segs = merge_n_segs(offsets);
+  auto Wc = merge_weights(W, base, n_models, n_segs);
+  TORCH_CHECK(dta_topk_merge_shmem(n_models, n_segs, int(block)) <=
+                  DTA_MERGE_LDS_LIMIT,
+              "topk merge: tiles + offsets + W do not fit the LDS budget of ",
+              DTA_MERGE_LDS_LIMIT, " B");
+  auto offs = merge_offsets(offsets, base);
+  launch_weighted_merge_topk(base.data_ptr<float>(), d, Wc.data_ptr<float>(),
+                             offs.data_ptr<int64_t>(), n_models, n_segs, P,
+                             out.data_ptr<float>(), stream());
+}
+
+Tensor grad_merge_weights_topk(Tensor g, Tensor base, Tensor data, int64_t k,
+                               int64_t block, Tensor merged, Tensor offsets) {
+  const int64_t P = base.numel();
+  check_plane(base, P, "base"); check_plane(merged, P, "merged");
+  const bool gb = check_grad_plane(g, P);
+  const TopkView d = topk_view(data, P, k, block);
+  const int n_models = merge_n_models(data.size(0));
+  const int n_segs = merge_n_segs(offsets);
+  auto ch = grad_w_chunks(offsets, base, n_segs);
+  const int n_chunks = int(ch.numel() / 3);
+  auto gw = torch::zeros({n_models, n_segs},
+                         base.options().dtype(torch::kFloat32));
+  launch_grad_merge_weights_topk(g.data_ptr(), gb, base.data_ptr<float>(), d,
+                                 merged.data_ptr<float>(),
+                                 ch.data_ptr<int64_t>(), n_models, n_chunks,
+                                 P, gw.data_ptr<float>(), n_segs, stream());
+  return gw;
+}
+
+void axpy_topk(Tensor w, Tensor data, int64_t k, int64_t block, int64_t row,
+               double alpha) {
+  const int64_t P = w.numel();
+  check_plane(w, P, "w");
+  const TopkView d = topk_view(data, P, k, block);
+  TORCH_CHECK(row >= 0 && row < data.size(0), "row out of range");
+  launch_axpy_topk(w.data_ptr<float>(), d, int(row), float(alpha), P,
+                   stream());
+}
+
 void weighted_merge_packed(Tensor base, Tensor data, Tensor scales,
                            int64_t block, Tensor W, Tensor offsets,
                            Tensor out) {
   const int64_t P = base.numel();
+  if (is_topk(data))
+    return weighted_merge_topk(base, data, topk_k_of(data, P, block), block,
+                               W, offsets, out);
   check_plane(base, P, "base"); check_plane(out, P, "out");
   const PackedView d = packed_view(data, scales, P, block);
   const int n_models = merge_n_models(data.size(0));
@@ -593,6 +714,9 @@ Tensor grad_merge_weights_packed(Tensor g, Tensor base, Tensor data,
                                  Tensor scales, int64_t block, Tensor merged,
                                  Tensor offsets) {
   const int64_t P = base.numel();
+  if (is_topk(data))
+    return grad_merge_weights_topk(g, base, data, topk_k_of(data, P, block),
+                                   block, merged, offsets);
   check_plane(base, P, "base"); check_plane(merged, P, "merged");
   const bool gb = check_grad_plane(g, P);
   TORCH_CHECK(aligned16(g), "g must be 16-byte aligned");
@@ -613,6 +737,8 @@ Tensor grad_merge_weights_packed(Tensor g, Tensor base, Tensor data,
 void axpy_packed(Tensor w, Tensor data, Tensor scales, int64_t block,
                  int64_t row, double alpha) {
   const int64_t P = w.numel();
+  if (is_topk(data))
+    return axpy_topk(w, data, topk_k_of(data, P, block), block, row, alpha);
   check_plane(w, P, "w");
   const PackedView d = packed_view(data, scales, P, block);
   TORCH_CHECK(row >= 0 && row < data.size(0), "row out of range");
@@ -621,8 +747,20 @@ void axpy_packed(Tensor w, Tensor data, Tensor scales, int64_t block,
 }
 
 // (codes [nb*block] int8, scales [nb] fp32) of x - base, or of x when base
-// is empty
-std::vector<Tensor> quantize_int8(Tensor x, Tensor base, int64_t block) {
+// is empty. topk_k > 0: the top-k form of the same delta instead, {entries
+// [nb*topk_k] int32} of (x - base) + residual_in, with the remainder
+// written to residual_out (each used when given and not empty)
+std::vector<Tensor> quantize_int8(Tensor x, Tensor base, int64_t block,
+                                  int64_t topk_k,
+                                  std::optional<Tensor> residual_in,
+                                  std::optional<Tensor> residual_out) {
+  if (topk_k != 0) {
+    const Tensor none = x.new_empty({0});
+    return {topk_compress(x, base, residual_in.value_or(none),
+                          residual_out.value_or(none), topk_k, block)};
+  }
+  TORCH_CHECK(!residual_in && !residual_out,
+              "quantize_int8: a residual belongs to the top-k form");
   check_f32(x, "x");
   const int64_t P = x.numel();
   TORCH_CHECK(P >= 1, "quantize_int8: empty input");
@@ -1241,7 +1379,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("weighted_merge_packed", &weighted_merge_packed);
   m.def("grad_merge_weights_packed", &grad_merge_weights_packed);
   m.def("axpy_packed", &axpy_packed);
-  m.def("quantize_int8", &quantize_int8);
+  m.def("quantize_int8", &quantize_int8, py::arg("x"), py::arg("base"),
+        py::arg("block"), py::arg("topk_k") = 0,
+        py::arg("residual_in") = py::none(),
+        py::arg("residual_out") = py::none());
   m.def("ce_fwd", &ce_fwd);
   m.def("ce_bwd", &ce_bwd);
   m.def("ce_fwd_bwd", &ce_fwd_bwd, pybind11::arg("logits"),

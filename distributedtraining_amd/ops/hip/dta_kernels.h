@@ -204,6 +204,43 @@ constexpr int DTA_QUANT_MAX_BLOCK = 16384;
 void launch_delta_quantize_int8(const float* w, const float* base, int64_t P,
                                 int block, int64_t nb, signed char* codes,
                                 float* scales, hipStream_t s);
+// Blockwise top-k with error feedback of d = (w - base) + residual_in (base
+// and residual_in may be null), bit-equal to comm.topk_compress_blockwise on
+// the CPU. entries [nb*k] int32, (idx << 16) | bf16 bits, ascending idx per
+// block; residual_out [P] (null: not written; may alias residual_in). block
+// a power of two in [DTA_TOPK_MIN_BLOCK, DTA_TOPK_MAX_BLOCK], k % 4 == 0,
+// 4 <= k <= block / 4; every pointer 16 B aligned. No host sync.
+constexpr int DTA_TOPK_MIN_BLOCK = 1024;
+constexpr int DTA_TOPK_MAX_BLOCK = 16384;
+void launch_delta_topk(const float* w, const float* base,
+                       const float* residual_in, float* residual_out,
+                       int64_t P, int block, int k, int64_t nb, int* entries,
+                       hipStream_t s);
+// Gathered top-k deltas: data [N, ld = nb*k] entries, block == 1 << shift.
+// Entries whose element lies past P are skipped. Each consumer produces what
+// its fp32 kernel produces on the densified rows, bit for bit (axpy: as
+// numbers; it touches only the elements on the support). base/out/w 16 B
+// aligned.
+struct TopkView {
+  const int* data;
+  int64_t ld;
+  int shift;
+  int k;
+};
+// dynamic LDS of the merge: two tiles of min(block, 4096) fp32 + offsets + W
+size_t dta_topk_merge_shmem(int n_models, int n_segs, int block);
+void launch_weighted_merge_topk(const float* base, const TopkView& d,
+                                const float* W, const int64_t* offsets,
+                                int n_models, int n_segs, int64_t P,
+                                float* out, hipStream_t s);
+void launch_grad_merge_weights_topk(const void* g, bool g_is_bf16,
+                                    const float* base, const TopkView& d,
+                                    const float* merged,
+                                    const int64_t* chunks, int n_models,
+                                    int n_chunks, int64_t P, float* grad_w,
+                                    int n_segs, hipStream_t s);
+void launch_axpy_topk(float* w, const TopkView& d, int row, float alpha,
+                      int64_t P, hipStream_t s);
 
 // ---- norms ----------------------------------------------------------------
 // dγ/dβ partial-panel geometry: for cols <= 1024 the partials come from

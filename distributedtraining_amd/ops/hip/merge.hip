@@ -20,6 +20,11 @@
 //
 // delta_quantize_int8_k makes the int8 form: one workgroup per quantisation
 // block, w and base read once, the fp32 delta never written.
+//
+// A fourth form is sparse: blockwise top-k entries (delta_topk_k makes them,
+// with an error-feedback residual). delta_at cannot express it; its three
+// consumers are kernels of their own further down and hold the same
+// contract, the fp32 kernel's bits on the densified rows.
 #include "dta_common.h"
 #include "dta_kernels.h"
 
@@ -328,6 +333,386 @@ __global__ void delta_quantize_int8_k(const float* __restrict__ w,
   }
 }
 
+// ---- blockwise top-k compressor ---------------------------------------------
+// entries / residual of d = (w - base) + residual_in (base, residual_in
+// optional), equal bit for bit to comm.topk_compress_blockwise on the CPU.
+// One workgroup per block, lane t owns elements 16t .. 16t+15 like the int8
+// quantiser, d lives in registers only. The key of an element is the bit
+// pattern of |d| (NaN sorts above +inf and is always kept).
+//   1. radix select of the k-th largest key T: four 8-bit passes, each a
+//      256-bin LDS histogram of the keys that still match the prefix (integer
+//      atomics: any order gives the same counts), wave 0 suffix-scans the
+//      bins and picks the digit. `need` keys equal to T are kept next to
+//      every key above it.
+//   2. one block-wide exclusive scan of (keys > T, keys == T) per lane, packed
+//      in one word: the ties are ranked in index order, the lowest `need`
+//      win, and a lane's first output slot is gt_before + min(ties_before,
+//      need), so the entries land in ascending idx.
+//   3. entries go through LDS and leave as 16 B stores; the residual leaves
+//      as the lane's four 16 B stores. A lane reads its own residual_in
+//      elements before it writes them, so the two may alias.
+// Every loop bound is block-uniform and no lane returns before a barrier.
+constexpr int TOPK_PER_LANE = 16;
+typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
+
+// bf16 bits of a float, round to nearest even ON THE BITS as the CPU
+// definition does it (a NaN is 0x7FC0): no dependence on the denormal mode
+DEV uint32_t topk_bf16_bits(uint32_t bits) {
+  if ((bits & 0x7FFFFFFFu) > 0x7F800000u) return 0x7FC0u;
+  return (bits + 0x7FFFu + ((bits >> 16) & 1u)) >> 16;
+}
+
+__global__ void delta_topk_k(const float* __restrict__ w,
+                             const float* __restrict__ base,
+                             const float* residual_in, float* residual_out,
+                             int64_t P, int block, int k,
+                             int* __restrict__ entries) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  uint32_t* s_ent = reinterpret_cast<uint32_t*>(smem);   // [k]
+  __shared__ uint32_t s_hist[256];
+  __shared__ uint32_t s_wave[16];
+  __shared__ uint32_t s_sel[2];
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int64_t e0 = int64_t(blockIdx.x) * block + tid * TOPK_PER_LANE;
+
+  float d[TOPK_PER_LANE];
+  if (e0 + TOPK_PER_LANE <= P) {
+#pragma unroll
+    for (int v = 0; v < TOPK_PER_LANE / 4; ++v) {
+      f32x4 a = *reinterpret_cast<const f32x4*>(w + e0 + 4 * v);
+      if (base != nullptr) {
+        const f32x4 b = *reinterpret_cast<const f32x4*>(base + e0 + 4 * v);
+        a = f32x4{a[0] - b[0], a[1] - b[1], a[2] - b[2], a[3] - b[3]};
+      }
+      if (residual_in != nullptr) {
+        const f32x4 r =
+            *reinterpret_cast<const f32x4*>(residual_in + e0 + 4 * v);
+        a = f32x4{a[0] + r[0], a[1] + r[1], a[2] + r[2], a[3] + r[3]};
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) d[4 * v + j] = a[j];
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < TOPK_PER_LANE; ++j) {
+      const int64_t e = e0 + j;
+      float a = 0.f;
+      if (e < P) {
+        a = base != nullptr ? w[e] - base[e] : w[e];
+        if (residual_in != nullptr) a = a + residual_in[e];
+      }
+      d[j] = a;
+    }
+  }
+  uint32_t key[TOPK_PER_LANE];
+#pragma unroll
+  for (int j = 0; j < TOPK_PER_LANE; ++j)
+    key[j] = __float_as_uint(d[j]) & 0x7FFFFFFFu;
+
+  for (int b = tid; b < 256; b += blockDim.x) s_hist[b] = 0;
+  // ---- 1. radix select ------------------------------------------------------
+  uint32_t prefix = 0, need = uint32_t(k);
+#pragma unroll
+  for (int shift = 24; shift >= 0; shift -= 8) {
+    const uint32_t hi_mask = shift == 24 ? 0u : (0xFFFFFFFFu << (shift + 8));
+    __syncthreads();            // bins zeroed, s_sel of the last pass read
+    // neighbours mostly share a digit: one atomic per run of equal digits
+    int cur = -1;
+    uint32_t run = 0;
+#pragma unroll
+    for (int j = 0; j < TOPK_PER_LANE; ++j) {
+      if (((key[j] ^ prefix) & hi_mask) == 0) {
+        const int bin = int((key[j] >> shift) & 255u);
+        if (bin == cur) {
+          ++run;
+        } else {
+          if (run) atomicAdd(&s_hist[cur], run);
+          cur = bin;
+          run = 1;
+        }
+      }
+    }
+    if (run) atomicAdd(&s_hist[cur], run);
+    __syncthreads();
+    if (wid == 0) {
+      // lane l owns bins 4l .. 4l+3; above = count in the bins of lanes > l
+      uint32_t c[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) c[j] = s_hist[4 * lane + j];
+      const uint32_t mine = c[0] + c[1] + c[2] + c[3];
+      uint32_t suf = mine;
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t other = uint32_t(__shfl_down(int(suf), o));
+        if (lane + o < 64) suf += other;
+      }
+      uint32_t gt = suf - mine;
+#pragma unroll
+      for (int j = 3; j >= 0; --j) {
+        // exactly one bin of the 256 has gt < need <= gt + count
+        if (gt < need && need <= gt + c[j]) {
+          s_sel[0] = uint32_t(4 * lane + j);
+          s_sel[1] = need - gt;
+        }
+        gt += c[j];
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) s_hist[4 * lane + j] = 0;
+    }
+    __syncthreads();
+    prefix |= s_sel[0] << shift;
+    need = s_sel[1];
+  }
+  const uint32_t T = prefix;    // the k-th largest key; `need` ties are kept
+
+  // ---- 2. slots -------------------------------------------------------------
+  uint32_t cnt = 0;             // (keys == T) << 16 | (keys > T)
+#pragma unroll
+  for (int j = 0; j < TOPK_PER_LANE; ++j)
+    cnt += (key[j] > T ? 1u : 0u) + (key[j] == T ? 0x10000u : 0u);
+  uint32_t inc = cnt;           // inclusive scan inside the wave
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const uint32_t other = uint32_t(__shfl_up(int(inc), o));
+    if (lane >= o) inc += other;
+  }
+  if (lane == 63) s_wave[wid] = inc;
+  __syncthreads();
+  uint32_t before = inc - cnt;
+#pragma unroll
+  for (int q = 0; q < 16; ++q)
+    if (q < wid) before += s_wave[q];
+  uint32_t tie_rank = before >> 16;
+  uint32_t slot = (before & 0xFFFFu) + (tie_rank < need ? tie_rank : need);
+
+  // ---- 3. entries and residual ---------------------------------------------
+  float res[TOPK_PER_LANE];
+#pragma unroll
+  for (int j = 0; j < TOPK_PER_LANE; ++j) {
+    bool keep = key[j] > T;
+    if (key[j] == T) {
+      keep = tie_rank < need;
+      ++tie_rank;
+    }
+    float r = d[j];
+    // slot < k always: the kept elements of the block are exactly k
+    if (keep && slot < uint32_t(k)) {
+      const uint32_t bf = topk_bf16_bits(__float_as_uint(d[j]));
+      s_ent[slot++] = (uint32_t(tid * TOPK_PER_LANE + j) << 16) | bf;
+      r = d[j] - __uint_as_float(bf << 16);
+    }
+    if ((__float_as_uint(r) & 0x7F800000u) == 0x7F800000u) r = 0.f;
+    res[j] = r;
+  }
+  if (residual_out != nullptr) {
+    if (e0 + TOPK_PER_LANE <= P) {
+#pragma unroll
+      for (int v = 0; v < TOPK_PER_LANE / 4; ++v)
+        *reinterpret_cast<f32x4*>(residual_out + e0 + 4 * v) = f32x4{
+            res[4 * v], res[4 * v + 1], res[4 * v + 2], res[4 * v + 3]};
+    } else {
+#pragma unroll
+      for (int j = 0; j < TOPK_PER_LANE; ++j)
+        if (e0 + j < P) residual_out[e0 + j] = res[j];
+    }
+  }
+  __syncthreads();
+  u32x4* dst = reinterpret_cast<u32x4*>(entries + int64_t(blockIdx.x) * k);
+  for (int v = tid; v < k / 4; v += blockDim.x)
+    dst[v] = *reinterpret_cast<const u32x4*>(s_ent + 4 * v);
+}
+
+// ---- top-k deltas: the three consumers ---------------------------------------
+// data: int32 [N, ld = nb*k] entries (idx << 16 | bf16 bits), k per block of
+// 1 << shift elements, ascending idx. Each result equals the fp32 kernel on
+// the densified rows bit for bit: the kernels below densify one (row, tile)
+// at a time in LDS and then do per element exactly what the dense kernels
+// do. A tile is min(block, TOPK_TILE) elements; a block wider than a tile is
+// walked tile by tile, every tile looking through all k entries of its
+// block. Two tiles alternate, so one barrier covers a scatter: a lane zeroes
+// the tile elements it has just read (nobody else reads them), which leaves
+// that tile clean for the scatter after the next barrier.
+constexpr int TOPK_TILE = 4096;
+constexpr int TOPK_THREADS = 256;
+constexpr int TOPK_VECS = TOPK_TILE / (4 * TOPK_THREADS);   // per lane
+
+struct TopkArgs {
+  const int* data;
+  int64_t ld;
+  int shift, k, tile;
+};
+
+// entries of row i that fall into [lo, hi) of the tile starting at t0 go to
+// their place in `tile` (fp32 [a.tile], clean on entry)
+DEV void topk_scatter(const TopkArgs& a, int i, int64_t t0, int64_t lo,
+                      int64_t hi, float* tile) {
+  const int64_t blk = t0 >> a.shift;
+  const int64_t b0 = blk << a.shift;
+  const int* ent = a.data + int64_t(i) * a.ld + blk * a.k;
+  for (int j = threadIdx.x; j < a.k; j += blockDim.x) {
+    const uint32_t en = uint32_t(ent[j]);
+    const int64_t e = b0 + int64_t(en >> 16);
+    // hi <= P and hi <= t0 + tile: entries past the plane or outside the
+    // tile are skipped here
+    if (e >= lo && e < hi) tile[e - t0] = __uint_as_float(en << 16);
+  }
+}
+
+__global__ void __launch_bounds__(TOPK_THREADS)
+weighted_merge_topk_k(const float* __restrict__ base, TopkArgs a,
+                      const float* __restrict__ W,
+                      const int64_t* __restrict__ offsets, int n_models,
+                      int n_segs, int64_t P, float* __restrict__ out) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* s_tile = reinterpret_cast<float*>(smem);          // [2][a.tile]
+  int64_t* s_off = reinterpret_cast<int64_t*>(smem + 2 * a.tile * 4);
+  float* s_w = reinterpret_cast<float*>(
+      smem + 2 * a.tile * 4 + (n_segs + 1) * sizeof(int64_t) +
+      ((n_segs + 1) & 1) * 8);
+  for (int i = threadIdx.x; i <= n_segs; i += blockDim.x)
+    s_off[i] = offsets[i];
+  for (int i = threadIdx.x; i < n_models * n_segs; i += blockDim.x)
+    s_w[i] = W[i];
+  for (int i = threadIdx.x; i < 2 * a.tile; i += blockDim.x) s_tile[i] = 0.f;
+  __syncthreads();
+
+  const int64_t n_tiles = (P + a.tile - 1) / a.tile;
+  for (int64_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {
+    const int64_t t0 = t * a.tile;
+    const int64_t hi = t0 + a.tile < P ? t0 + a.tile : P;
+    int seg[TOPK_VECS][4];
+    float b[TOPK_VECS][4], acc[TOPK_VECS][4];
+#pragma unroll
+    for (int v = 0; v < TOPK_VECS; ++v) {
+      const int64_t e = t0 + (threadIdx.x + v * TOPK_THREADS) * 4;
+      const bool live = (threadIdx.x + v * TOPK_THREADS) * 4 < a.tile;
+      if (live && e + 4 <= P) {
+        const f32x4 vb = *reinterpret_cast<const f32x4*>(base + e);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) b[v][j] = vb[j];
+      } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          b[v][j] = (live && e + j < P) ? base[e + j] : 0.f;
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        // past the plane: any valid segment, the element is never stored
+        const int64_t ej = e + j < P ? e + j : P - 1;
+        seg[v][j] = (j > 0 && ej < s_off[seg[v][j - 1] + 1])
+                        ? seg[v][j - 1] : find_seg(s_off, n_segs, ej);
+        acc[v][j] = 0.f;
+      }
+    }
+    topk_scatter(a, 0, t0, t0, hi, s_tile);
+    for (int i = 0; i < n_models; ++i) {
+      __syncthreads();
+      float* cur = s_tile + (i & 1) * a.tile;
+      if (i + 1 < n_models)
+        topk_scatter(a, i + 1, t0, t0, hi, s_tile + ((i + 1) & 1) * a.tile);
+#pragma unroll
+      for (int v = 0; v < TOPK_VECS; ++v) {
+        const int l = (threadIdx.x + v * TOPK_THREADS) * 4;
+        if (l < a.tile) {
+          const f32x4 dv = *reinterpret_cast<const f32x4*>(cur + l);
+          *reinterpret_cast<f32x4*>(cur + l) = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            acc[v][j] = fmaf(s_w[i * n_segs + seg[v][j]], b[v][j] + dv[j],
+                             acc[v][j]);
+        }
+      }
+    }
+#pragma unroll
+    for (int v = 0; v < TOPK_VECS; ++v) {
+      const int l = (threadIdx.x + v * TOPK_THREADS) * 4;
+      const int64_t e = t0 + l;
+      if (l < a.tile) {
+        if (e + 4 <= P) {
+          *reinterpret_cast<f32x4*>(out + e) =
+              f32x4{acc[v][0], acc[v][1], acc[v][2], acc[v][3]};
+        } else {
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            if (e + j < P) out[e + j] = acc[v][j];
+        }
+      }
+    }
+    __syncthreads();   // tile 0 is clean before the next scatter into it
+  }
+}
+
+// grid = (chunks, n_models) and lane t sums start + t, + 256, ... in
+// ascending order, as grad_w_k does. A chunk starts at a segment offset, so
+// it is walked over the tiles it overlaps; only entries inside the chunk are
+// scattered, so every scattered element is read, and zeroed, by its lane.
+template <bool G_BF16>
+__global__ void __launch_bounds__(GW_THREADS)
+grad_w_topk_k(const void* __restrict__ gp, const float* __restrict__ base,
+              TopkArgs a, const float* __restrict__ merged,
+              const int64_t* __restrict__ chunks, int n_segs, int64_t P,
+              float* __restrict__ grad_w) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* s_tile = reinterpret_cast<float*>(smem);          // [2][a.tile]
+  __shared__ float lds[16];
+  const int64_t start = chunks[blockIdx.x * 3 + 0];
+  const int64_t end = chunks[blockIdx.x * 3 + 1];
+  const int seg = int(chunks[blockIdx.x * 3 + 2]);
+  const int i = blockIdx.y;
+  for (int j = threadIdx.x; j < 2 * a.tile; j += blockDim.x) s_tile[j] = 0.f;
+  __syncthreads();
+  float acc = 0.f;
+  int64_t e = start + threadIdx.x;
+  const int64_t t_first = start / a.tile;
+  const int64_t t_end = (end + a.tile - 1) / a.tile;   // start == end: none
+  if (t_first < t_end)
+    topk_scatter(a, i, t_first * a.tile, start,
+                 end < (t_first + 1) * a.tile ? end : (t_first + 1) * a.tile,
+                 s_tile);
+  for (int64_t t = t_first; t < t_end; ++t) {
+    __syncthreads();
+    const int64_t t0 = t * a.tile;
+    const int64_t hi = end < t0 + a.tile ? end : t0 + a.tile;
+    float* cur = s_tile + ((t - t_first) & 1) * a.tile;
+    if (t + 1 < t_end)
+      topk_scatter(a, i, t0 + a.tile, t0 + a.tile,
+                   end < t0 + 2 * int64_t(a.tile) ? end
+                                                  : t0 + 2 * int64_t(a.tile),
+                   s_tile + ((t + 1 - t_first) & 1) * a.tile);
+    // the plain loop of grad_w_k. Loading 8 elements ahead with predicated
+    // loads measured 5.95 ms against 3.38 ms for this form
+    // (profiles/r09_topk_deltas.md).
+    for (; e < hi; e += GW_THREADS) {
+      const float g = G_BF16 ? bf2f(reinterpret_cast<const ushort*>(gp)[e])
+                             : reinterpret_cast<const float*>(gp)[e];
+      const float d = cur[e - t0];
+      cur[e - t0] = 0.f;
+      acc = fmaf(g, (base[e] - merged[e]) + d, acc);
+    }
+  }
+  acc = block_sum<16>(acc, lds);
+  if (threadIdx.x == 0) atomicAdd(grad_w + int64_t(i) * n_segs + seg, acc);
+}
+
+// w[e] = fma(alpha, v, w[e]) over the in-range entries of one row: the
+// indices of a row are unique, so plain stores. Four entries per lane (one
+// 16 B load; k % 4 == 0 keeps them in one block).
+__global__ void axpy_topk_k(float* __restrict__ w, TopkArgs a, int row,
+                            float alpha, int64_t P) {
+  const int* ent = a.data + int64_t(row) * a.ld;
+  int64_t q = (int64_t(blockIdx.x) * blockDim.x + threadIdx.x) * 4;
+  const int64_t stride = int64_t(gridDim.x) * blockDim.x * 4;
+  for (; q < a.ld; q += stride) {
+    const u32x4 en = *reinterpret_cast<const u32x4*>(ent + q);
+    const int64_t b0 = (q / a.k) << a.shift;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int64_t e = b0 + int64_t(en[j] >> 16);
+      if (e < P) w[e] = fmaf(alpha, __uint_as_float(en[j] << 16), w[e]);
+    }
+  }
+}
+
 size_t merge_shmem(int n_models, int n_segs) {
   return (n_segs + 1) * sizeof(int64_t) + 8 +
          size_t(n_models) * n_segs * sizeof(float);
@@ -434,4 +819,65 @@ void launch_delta_quantize_int8(const float* w, const float* base, int64_t P,
   if (threads < 64) threads = 64;
   delta_quantize_int8_k<<<unsigned(nb), threads, 0, s>>>(w, base, P, block,
                                                          codes, scales);
+}
+
+// ---- top-k deltas -------------------------------------------------------------
+namespace {
+TopkArgs topk_args(const TopkView& d) {
+  const int block = 1 << d.shift;
+  return TopkArgs{d.data, d.ld, d.shift, d.k,
+                  block < TOPK_TILE ? block : TOPK_TILE};
+}
+}  // namespace
+
+size_t dta_topk_merge_shmem(int n_models, int n_segs, int block) {
+  return 2 * sizeof(float) * size_t(block < TOPK_TILE ? block : TOPK_TILE) +
+         merge_shmem(n_models, n_segs);
+}
+
+void launch_delta_topk(const float* w, const float* base,
+                       const float* residual_in, float* residual_out,
+                       int64_t P, int block, int k, int64_t nb, int* entries,
+                       hipStream_t s) {
+  const int threads = block / TOPK_PER_LANE;
+  const size_t shmem = size_t(k) * sizeof(int);
+  delta_topk_k<<<unsigned(nb), threads, shmem, s>>>(
+      w, base, residual_in, residual_out, P, block, k, entries);
+}
+
+void launch_weighted_merge_topk(const float* base, const TopkView& d,
+                                const float* W, const int64_t* offsets,
+                                int n_models, int n_segs, int64_t P,
+                                float* out, hipStream_t s) {
+  const TopkArgs a = topk_args(d);
+  const int64_t n_tiles = (P + a.tile - 1) / a.tile;
+  const int grid =
+      int(n_tiles < MAX_RESIDENT_BLOCKS ? n_tiles : MAX_RESIDENT_BLOCKS);
+  const size_t shmem = dta_topk_merge_shmem(n_models, n_segs, 1 << d.shift);
+  weighted_merge_topk_k<<<grid, TOPK_THREADS, shmem, s>>>(
+      base, a, W, offsets, n_models, n_segs, P, out);
+}
+
+void launch_grad_merge_weights_topk(const void* g, bool g_is_bf16,
+                                    const float* base, const TopkView& d,
+                                    const float* merged,
+                                    const int64_t* chunks, int n_models,
+                                    int n_chunks, int64_t P, float* grad_w,
+                                    int n_segs, hipStream_t s) {
+  const TopkArgs a = topk_args(d);
+  dim3 grid(n_chunks, n_models);
+  const size_t shmem = 2 * sizeof(float) * size_t(a.tile);
+  if (g_is_bf16)
+    grad_w_topk_k<true><<<grid, GW_THREADS, shmem, s>>>(
+        g, base, a, merged, chunks, n_segs, P, grad_w);
+  else
+    grad_w_topk_k<false><<<grid, GW_THREADS, shmem, s>>>(
+        g, base, a, merged, chunks, n_segs, P, grad_w);
+}
+
+void launch_axpy_topk(float* w, const TopkView& d, int row, float alpha,
+                      int64_t P, hipStream_t s) {
+  const int block = 256;
+  const int grid = elementwise_grid(d.ld, block, 4);
+  axpy_topk_k<<<grid, block, 0, s>>>(w, topk_args(d), row, alpha, P);
 }

@@ -48,6 +48,82 @@ def dequantize_blockwise_int8(q: torch.Tensor, scale: torch.Tensor,
     return x.view(-1)[:numel]
 
 
+TOPK_MIN_BLOCK = 1024
+TOPK_MAX_BLOCK = 16384
+_NAN_BF16 = 0x7FC0
+
+
+def check_topk_format(k: int, block: int) -> None:
+    """The top-k wire format's limits: ``block`` a power of two in
+    [1024, 16384], ``k`` a multiple of 4 in [4, block / 4]."""
+    if not (isinstance(block, int) and TOPK_MIN_BLOCK <= block
+            <= TOPK_MAX_BLOCK and block & (block - 1) == 0):
+        raise ValueError(f"topk block must be a power of two in "
+                         f"[{TOPK_MIN_BLOCK}, {TOPK_MAX_BLOCK}], got {block!r}")
+    if not (isinstance(k, int) and k % 4 == 0 and 4 <= k <= block // 4):
+        raise ValueError(f"topk k must be a multiple of 4 in [4, block/4 = "
+                         f"{block // 4}], got {k!r}")
+
+
+def topk_compress_blockwise(flat: torch.Tensor, k: int, block: int = 4096,
+                            residual: Optional[torch.Tensor] = None):
+    """Blockwise top-k with error feedback, the definition the GPU kernel is
+    held to bit for bit.
+
+    ``d = flat + residual`` is cut into blocks of ``block`` elements (zero
+    padded). Each block keeps the ``k`` elements of largest magnitude: the
+    key is the bit pattern of ``|d|`` (unsigned order is float order, every
+    NaN sorts above +inf and so is always kept), ties go to the lower index
+    (a stable descending sort, never ``torch.topk``). An entry is the int32
+    ``(idx << 16) | bf16_bits(value)``, ``idx`` the offset in the block and
+    the value rounded to nearest even (a NaN is sent as 0x7FC0); entries of
+    a block ascend in ``idx``. Entries of a ragged last block may point past
+    the end of the plane; their value bits are 0.
+
+    Returns ``(entries int32 [nb*k], residual_out fp32 [P])``.
+    ``residual_out`` is ``d - float(bf16(d))`` where an element was kept
+    (exact in fp32) and ``d`` where it was dropped, and 0 wherever that is
+    not finite: poison is sent once and not carried. For finite ``d``,
+    densified entries + ``residual_out`` == ``d``.
+    """
+    check_topk_format(k, block)
+    d = flat.to(torch.float32)
+    d = d + residual.to(torch.float32) if residual is not None else d.clone()
+    n = d.numel()
+    nb = (n + block - 1) // block
+    x = torch.nn.functional.pad(d, (0, nb * block - n)).view(nb, block)
+    key = x.view(torch.int32) & 0x7FFFFFFF
+    order = torch.sort(key, dim=1, descending=True, stable=True).indices
+    idx = torch.sort(order[:, :k], dim=1).values             # [nb, k] int64
+    bits = x.gather(1, idx).view(torch.int32)
+    # round to nearest even on the bits; NaN has one spelling on the wire
+    bf = ((bits + (0x7FFF + ((bits >> 16) & 1))) >> 16) & 0xFFFF
+    bf = torch.where(key.gather(1, idx) > 0x7F800000,
+                     torch.full_like(bf, _NAN_BF16), bf)
+    entries = ((idx.to(torch.int32) << 16) | bf).reshape(-1)
+    sent = (bf << 16).view(torch.float32)
+    res = x.clone()
+    res.scatter_(1, idx, x.gather(1, idx) - sent)
+    res = res.view(-1)[:n]
+    res = torch.where(torch.isfinite(res), res, torch.zeros_like(res))
+    return entries, res.contiguous()
+
+
+def topk_densify(entries: torch.Tensor, k: int, numel: int,
+                 block: int = 4096) -> torch.Tensor:
+    """fp32 [numel] of one row of top-k entries: a scatter into zeros that
+    skips the entries past the end of the plane."""
+    ent = entries.view(-1, k)
+    nb = ent.shape[0]
+    idx = (ent >> 16).to(torch.int64) + torch.arange(
+        nb, device=ent.device).unsqueeze(1) * block
+    val = ((ent & 0xFFFF) << 16).view(torch.float32)
+    keep = idx < numel
+    out = torch.zeros(numel, dtype=torch.float32, device=ent.device)
+    out[idx[keep]] = val[keep]
+    return out
+
+
 @dataclass
 class PackedDeltas:
     """N gathered deltas kept in their wire form (the resident gather under
@@ -55,7 +131,10 @@ class PackedDeltas:
 
     ``kind`` "fp32" / "bf16": ``data`` is [N, P]. ``kind`` "int8": ``data``
     is [N, nb*block] codes and ``scales`` [N, nb] fp32 (the layout of
-    :func:`quantize_blockwise_int8`, one row per rank). ``numel`` is P.
+    :func:`quantize_blockwise_int8`, one row per rank). ``kind`` "topk":
+    ``data`` is int32 [N, nb*k], ``k`` entries per block of ``block``
+    elements (the layout of :func:`topk_compress_blockwise`); ``scales`` is
+    unused. ``numel`` is P.
 
     ``ops.weighted_merge``, ``ops.grad_merge_weights`` and ``ops.axpy_``
     take the container where they take an [N, P] tensor and dequantise in
@@ -67,15 +146,22 @@ class PackedDeltas:
     numel: int
     scales: Optional[torch.Tensor] = None
     block: int = 4096
+    k: int = 128
 
     def __post_init__(self):
-        if self.kind not in ("fp32", "bf16", "int8"):
+        if self.kind not in ("fp32", "bf16", "int8", "topk"):
             raise ValueError(f"unknown PackedDeltas kind {self.kind!r}")
         want = {"fp32": torch.float32, "bf16": torch.bfloat16,
-                "int8": torch.int8}[self.kind]
+                "int8": torch.int8, "topk": torch.int32}[self.kind]
         if self.data.dim() != 2 or self.data.dtype != want:
             raise ValueError(f"{self.kind} deltas need a 2-d {want} tensor")
-        if self.kind == "int8":
+        if self.kind == "topk":
+            check_topk_format(self.k, self.block)
+            nb = (self.numel + self.block - 1) // self.block
+            if self.data.shape[1] != nb * self.k:
+                raise ValueError("topk deltas need entries [N, nb*k], "
+                                 "nb = ceil(numel / block)")
+        elif self.kind == "int8":
             nb = (self.numel + self.block - 1) // self.block
             if self.scales is None or self.data.shape[1] != nb * self.block \
                     or tuple(self.scales.shape) != (self.data.shape[0], nb):
@@ -86,10 +172,15 @@ class PackedDeltas:
 
     @classmethod
     def pack(cls, deltas: torch.Tensor, kind: str,
-             block: int = 4096) -> "PackedDeltas":
+             block: int = 4096, k: int = 128) -> "PackedDeltas":
         """Compress an [N, P] fp32 stack row by row (tests, tools)."""
         from .. import ops
         n, P = deltas.shape
+        if kind == "topk":
+            rows = [ops.topk_compress_blockwise(
+                deltas[i].contiguous(), k, block, update_residual=False)[0]
+                for i in range(n)]
+            return cls("topk", torch.stack(rows), P, None, block, k)
         if kind == "fp32":
             return cls("fp32", deltas.to(torch.float32).contiguous(), P)
         if kind == "bf16":
@@ -111,6 +202,12 @@ class PackedDeltas:
         """Row ``i`` as a fresh fp32 [P] tensor — the only O(P) temporary a
         consumer of packed deltas may make."""
         from .. import ops
+        if self.kind == "topk":
+            if ops.use_hip(self.data):
+                out = torch.zeros(self.numel, dtype=torch.float32,
+                                  device=self.data.device)
+                return ops.axpy_(out, (self, i), 1.0)
+            return topk_densify(self.data[i], self.k, self.numel, self.block)
         if self.kind == "int8":
             return ops.dequantize_blockwise_int8(
                 self.data[i], self.scales[i], self.numel, self.block)
@@ -213,15 +310,27 @@ class CommPlane:
 
     def all_gather_packed(self, flat: torch.Tensor, kind: str,
                           block: int = 4096,
-                          base: Optional[torch.Tensor] = None
-                          ) -> PackedDeltas:
+                          base: Optional[torch.Tensor] = None,
+                          residual: Optional[torch.Tensor] = None,
+                          update_residual: bool = True,
+                          k: int = 128) -> PackedDeltas:
         """Gather every rank's delta and KEEP it in wire form. The delta is
         ``flat``, or ``flat - base`` when ``base`` is given (int8 then
         quantises straight from the two planes in one kernel and the fp32
         delta is never written). int8: the two gathers of
-        :meth:`all_gather_flat_int8`; bf16: one cast, one gather."""
+        :meth:`all_gather_flat_int8`; bf16: one cast, one gather. topk:
+        :func:`topk_compress_blockwise` of the delta plus ``residual`` (which
+        is rewritten in place unless ``update_residual`` is False), ``k``
+        entries per ``block``, and one gather of the int32 entries:
+        nb * k * 4 bytes per rank."""
         from .. import ops
         n = flat.numel()
+        if kind == "topk":
+            ent, _ = ops.topk_compress_blockwise(
+                flat, k, block, base=base, residual=residual,
+                update_residual=update_residual)
+            return PackedDeltas("topk", self.all_gather_flat(ent), n, None,
+                                block, k)
         if kind == "int8":
             q, scale = ops.quantize_blockwise_int8(flat, block, base=base)
             return PackedDeltas("int8", self.all_gather_flat(q), n,

@@ -10,8 +10,8 @@ miner→HF-hub→averager→HF-hub→miner round trip.
 Collective choice per strategy (see merge_round): mean/nesterov use an
 all-reduce (O(P) resident — mandatory at Llama scale); score-weighted,
 meta-learned and genetic use an all-gather (every delta HBM-resident,
-optionally bf16/int8 on the wire, and with comm.resident_dtype = "wire"
-also bf16/int8 in HBM). Deterministic merges are computed
+optionally bf16/int8/top-k on the wire, and with comm.resident_dtype =
+"wire" also in that form in HBM). Deterministic merges are computed
 redundantly by every rank (identical bases, no broadcast); the
 meta-learned and genetic merges run on rank 0 (they need val-loss
 evaluations) and are broadcast (C2/C5).
@@ -25,7 +25,7 @@ from typing import Dict, List, Optional
 import torch
 
 from ..config import Config
-from ..parallel.comm import CommPlane, PackedDeltas
+from ..parallel.comm import CommPlane, PackedDeltas, check_topk_format
 from ..parallel.flat import FlatParams
 from ..roles.averager import ParameterizedAverager
 from ..roles.miner import DeltaLoop
@@ -56,6 +56,22 @@ class LocalSGDNode:
         self.merge_rounds = 0
         self._validator: Optional[DeltaValidator] = None
         self._validator_base = None   # base tensor identity at last refresh
+        # top-k error feedback: what this miner has not sent yet, fp32 [P],
+        # made on first use and zeroed with every fresh initial base
+        self.residual: Optional[torch.Tensor] = None
+        if self._topk():
+            check_topk_format(cfg.comm.topk_k, cfg.comm.topk_block)
+
+    def _topk(self) -> bool:
+        return self.cfg.comm.exchange_dtype == "topk"
+
+    def _topk_residual(self) -> Optional[torch.Tensor]:
+        if not self.cfg.comm.topk_error_feedback:
+            return None
+        if self.residual is None:
+            self.residual = torch.zeros_like(self.fp.master,
+                                             dtype=torch.float32)
+        return self.residual
 
     def _wire_dtype(self):
         return (torch.bfloat16 if self.cfg.comm.exchange_dtype == "bf16"
@@ -73,14 +89,27 @@ class LocalSGDNode:
         wire form: make_delta's fp32 plane is never written)."""
         if self._resident_wire() and self.cfg.comm.exchange_dtype == "int8":
             return None
+        if self._topk():
+            return None
         return self.fp.make_delta(base).flat    # fused θ−θ_base
 
     def _gather_deltas(self, flat: Optional[torch.Tensor],
-                       base: Optional[torch.Tensor] = None):
+                       base: Optional[torch.Tensor] = None,
+                       update_residual: bool = True):
         """All-gather the flat delta at the configured wire dtype. Returns
         [world, P] fp32 for the merge math, or under comm.resident_dtype =
         "wire" a PackedDeltas still in wire form. ``flat`` None (see
-        _local_delta): the delta is fp.master − ``base``."""
+        _local_delta): the delta is fp.master − ``base``. top-k compresses
+        fp.master − ``base`` plus the residual, which takes what was not sent
+        unless ``update_residual`` is False (a round that only scores)."""
+        if self._topk():
+            c = self.cfg.comm
+            packed = self.comm.all_gather_packed(
+                self.fp.master, "topk", block=c.topk_block, base=base,
+                residual=self._topk_residual(),
+                update_residual=update_residual and c.topk_error_feedback,
+                k=c.topk_k)
+            return packed if self._resident_wire() else packed.dequantize()
         if self._resident_wire():
             if flat is None:
                 return self.comm.all_gather_packed(
@@ -97,6 +126,8 @@ class LocalSGDNode:
         self.comm.broadcast_flat(self.fp.master, src=0)
         self.fp.sync_work_from_master()
         self.miner.install_base(self.fp.master)
+        if self.residual is not None:
+            self.residual.zero_()
 
     def train_steps(self, n: int) -> float:
         last = None
@@ -170,10 +201,13 @@ class LocalSGDNode:
         loop (validation_logic.py:126-139). Normalization happens
         identically on every rank from the gathered totals."""
         base = self.miner.base
-        if self._resident_wire():
+        if self._resident_wire() or self._topk():
             # the configured wire dtype applies to validation too, and the
-            # gather stays in that form (rows are applied by ops.axpy_)
-            deltas = self._gather_deltas(self._local_delta(base), base)
+            # gather stays in that form (rows are applied by ops.axpy_).
+            # top-k reads the residual and leaves it alone: the merge round
+            # that follows sends this delta again and must count it once
+            deltas = self._gather_deltas(self._local_delta(base), base,
+                                         update_residual=False)
         else:
             delta = self.fp.make_delta(base)
             deltas = self.comm.all_gather_flat(delta.flat)
