@@ -8,11 +8,14 @@ Every op has exactly two execution paths:
   ``torch.autograd.Function`` (see hip/*.hip). There is no eager fallback on
   GPU: missing extension ⇒ loud error (backend.require_ext).
 
-Plain projection GEMMs (QKV/out/MLP/LM-head matmuls) intentionally go to
-hipBLASLt (via ``ops.linear``: addmm with fused bias epilogue forward,
-custom colsum dbias + direct flat-plane wgrad accumulation backward), per
+Plain projection GEMMs (QKV/out/MLP/LM-head matmuls) go to hipBLASLt (via
+``ops.linear``: addmm with fused bias epilogue forward, dgrad backward), per
 the library-GEMM / hand-written-fused-op split; everything fused or
-memory-bound is ours.
+memory-bound is ours. One GEMM class is ours as well: the weight gradients
+``dW += dyᵀ·x`` of the shapes ``_wgrad_wins`` lists run on the split-K MFMA
+kernel of hip/wgrad.hip, which sums the bias gradient in the same pass over
+``dy``; every other weight gradient is a library GEMM accumulated directly
+into the flat plane, with the colsum kernel for its bias.
 
 Reference behavior being reimplemented: the implicit per-step op set of
 GPT-2 training in /root/reference.
@@ -52,6 +55,52 @@ __all__ = [
 import os as _os
 
 _USE_BGRADB = _os.environ.get("DTA_LT_BGRADB", "0") == "1"
+
+# Weight-gradient routing: "0" library GEMM + colsum everywhere (the path
+# before wgrad.hip), "1" the wgrad kernel wherever its shape contract holds,
+# anything else: the kernel only where _wgrad_wins measured it faster.
+_WGRAD = _os.environ.get("DTA_WGRAD", "auto")
+if _WGRAD not in ("0", "1"):
+    _WGRAD = "auto"
+
+
+def wgrad_route(mode: str) -> str:
+    """Switch the weight-gradient routing ("0", "1" or "auto"; tests flip it
+    in one process). Returns the previous setting."""
+    global _WGRAD
+    if mode not in ("0", "1", "auto"):
+        raise ValueError(f"wgrad_route: {mode!r}")
+    prev, _WGRAD = _WGRAD, mode
+    return prev
+
+
+# (T, out, in) at which tools/wgrad_ab.py measured the wgrad kernel faster than
+# addmm_ + colsum by more than the library arm's own spread (MI355X,
+# profiles/r10_wgrad.md). Unmeasured shapes stay on the library.
+_WGRAD_WINS: frozenset = frozenset(
+    (T, out, inp) for T in (65536, 32768)
+    for out, inp in ((2304, 768), (768, 768), (3072, 768), (768, 3072)))
+
+
+def _wgrad_wins(T: int, out: int, inp: int) -> bool:
+    return (T, out, inp) in _WGRAD_WINS
+
+
+def _wgrad_accum(m, dy2, x2, wgrad, bgrad, want_bias):
+    """dW (+ db) of one linear into the flat plane. -> (handled, db32):
+    handled False leaves everything to the library path; db32 is the fp32
+    bias gradient where a bias was wanted and bgrad is None."""
+    if _WGRAD == "0" or wgrad is None or dy2.dtype != torch.bfloat16:
+        return False, None
+    if _WGRAD == "auto" and not _wgrad_wins(
+            dy2.shape[0], dy2.shape[1], x2.shape[1]):
+        return False, None
+    if not (wgrad.is_contiguous() and m.wgrad.supported(dy2, x2)):
+        return False, None
+    db32 = m.wgrad.bias(dy2, x2, wgrad, bgrad if want_bias else None,
+                        want_bias and bgrad is None)
+    return True, (db32 if want_bias and bgrad is None else None)
+
 
 class _LinearFn(torch.autograd.Function):
     """F.linear semantics with two backward optimizations:
@@ -96,6 +145,9 @@ class _LinearFn(torch.autograd.Function):
                 return dx, None, db
             except RuntimeError:   # no epilogue kernel for this shape
                 pass
+        done, db32 = _wgrad_accum(m, dy2, x2, ctx.wgrad, ctx.bgrad, ctx.has_b)
+        if done:                            # dW and db from one pass over dy
+            return dx, None, _cast_grad(db32, w.dtype)
         if ctx.wgrad is not None:
             ctx.wgrad.addmm_(dy2.t(), x2)   # flat-plane accumulation
             dw = None
@@ -109,8 +161,10 @@ class _LinearFn(torch.autograd.Function):
 def linear(x: torch.Tensor, w: torch.Tensor,
            b: Optional[torch.Tensor] = None) -> torch.Tensor:
     """y = x @ w.T (+ b). hipBLASLt GEMM with fused bias epilogue forward;
-    backward: wgrad+bias-grad in one BGRADB-epilogue GEMM accumulated into
-    the flat-grad plane (colsum fallback).
+    backward: dgrad by the library; dW and the bias gradient accumulated into
+    the flat-grad plane by the wgrad kernel (hip/wgrad.hip) at the shapes of
+    _wgrad_wins, else by a library GEMM (beta = 1) + colsum (DTA_LT_BGRADB=1:
+    one BGRADB-epilogue GEMM).
 
     Serving decode (inference, tiny M): LATENCY-bound projections route
     to the hand-written GEMV; the big weight-streaming shapes stay on
@@ -239,16 +293,24 @@ class _MLPGeluFn(torch.autograd.Function):
         if dy2.stride(-1) != 1:
             dy2 = dy2.contiguous()
         dh = dy2.mm(w2)
-        if w2g is not None:
-            w2g.addmm_(dy2.t(), h)
-            dw2 = None
+        done, db32 = _wgrad_accum(m, dy2, h, w2g, b2g, True)
+        if done:
+            dw2, db2 = None, _cast_grad(db32, w2.dtype)
         else:
-            dw2 = dy2.t().mm(h)
-        db2 = _cast_grad(m.colsum(dy2, b2g), w2.dtype)
+            if w2g is not None:
+                w2g.addmm_(dy2.t(), h)
+                dw2 = None
+            else:
+                dw2 = dy2.t().mm(h)
+            db2 = _cast_grad(m.colsum(dy2, b2g), w2.dtype)
         dh_pre, db1 = m.gelu_bwd_colsum(dh, pre, b1g)
         del dh
         dx = dh_pre.mm(w1).view(ctx.xshape)
-        if w1g is not None:
+        # the fc bias already comes from gelu_bwd_colsum: no-bias kernel
+        done, _ = _wgrad_accum(m, dh_pre, x2, w1g, None, False)
+        if done:
+            dw1 = None
+        elif w1g is not None:
             w1g.addmm_(dh_pre.t(), x2)
             dw1 = None
         else:

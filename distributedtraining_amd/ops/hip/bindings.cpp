@@ -418,6 +418,87 @@ std::vector<Tensor> gelu_bwd_colsum(Tensor dy, Tensor x, OptTensor db_dst,
   return {dx, out};
 }
 
+// ---- weight gradient with the bias sum folded in (wgrad.hip) ---------------
+// The shape contract of wgrad_bias, in one place: dy [T, out] and x [T, in]
+// bf16 with unit column stride, row strides % 8 == 0 (the packed-qkv views
+// have a row stride larger than their width), 16 B aligned bases, T >= 1,
+// out a multiple of the tile's rows and in of its columns.
+const char* wgrad_reject(const Tensor& dy, const Tensor& x) {
+  if (!(dy.is_cuda() && x.is_cuda() && dy.device() == x.device()))
+    return "dy and x must be on one GPU";
+  if (dy.scalar_type() != torch::kBFloat16 ||
+      x.scalar_type() != torch::kBFloat16)
+    return "dy and x must be bf16";
+  if (dy.dim() != 2 || x.dim() != 2 || dy.size(0) != x.size(0))
+    return "dy must be [T, out] and x [T, in]";
+  const int64_t T = dy.size(0), out = dy.size(1), in = x.size(1);
+  if (T < 1 || T >= (int64_t(1) << 31)) return "T out of range";
+  if (out < DTA_WGRAD_BM || out % DTA_WGRAD_BM != 0 || in < DTA_WGRAD_BN ||
+      in % DTA_WGRAD_BN != 0 || out * in >= (int64_t(1) << 31))
+    return "out / in must be multiples of the tile";
+  if (dy.stride(1) != 1 || x.stride(1) != 1) return "unit column stride";
+  // T == 1: the row stride is never used
+  const int64_t lda = T > 1 ? dy.stride(0) : out, ldb = T > 1 ? x.stride(0) : in;
+  if (lda < out || ldb < in || lda % 8 != 0 || ldb % 8 != 0 ||
+      lda >= (int64_t(1) << 25) || ldb >= (int64_t(1) << 25))
+    return "row strides must be >= the width, % 8 == 0 and < 2^25";
+  if (reinterpret_cast<uintptr_t>(dy.data_ptr()) % 16 != 0 ||
+      reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 != 0)
+    return "16-byte aligned operands";
+  return nullptr;
+}
+bool wgrad_supported(Tensor dy, Tensor x) { return !wgrad_reject(dy, x); }
+std::vector<int64_t> wgrad_tile() {
+  return {DTA_WGRAD_BM, DTA_WGRAD_BN, DTA_WGRAD_BK};
+}
+int64_t wgrad_nsplit(int64_t T, int64_t out, int64_t in) {
+  return dta_wgrad_nsplit(
+      T, out, in, at::cuda::getCurrentDeviceProperties()->multiProcessorCount);
+}
+
+// dw = bf16(float(dw) + dy^T x) on the MFMA units, split over T and folded in
+// a fixed order (bit-repeatable); dw: bf16 [out, in] contiguous gradient view
+// of any alignment. The bias sum over t comes from the same pass over dy:
+// db given -> db = bf16(float(db) + sum), nothing returned; else bias_f32 ->
+// an fp32 [out] tensor is returned; else no bias is computed. nsplit 0: the
+// automatic split. Capturable: workspaces from the allocator, no host sync.
+Tensor wgrad_bias(Tensor dy, Tensor x, Tensor dw, OptTensor db, bool bias_f32,
+                  int64_t nsplit) {
+  const char* why = wgrad_reject(dy, x);
+  TORCH_CHECK(!why, "wgrad_bias: ", why ? why : "");
+  const int64_t T = dy.size(0), out = dy.size(1), in = x.size(1);
+  check_bf16(dw, "dw");
+  TORCH_CHECK(dw.device() == dy.device() && dw.dim() == 2 &&
+                  dw.size(0) == out && dw.size(1) == in,
+              "dw must be a contiguous bf16 [out, in] view on dy's device");
+  bf16_t* dbp = grad_dst(db, out, "db");
+  TORCH_CHECK(!dbp || db->device() == dy.device(), "db must be on dy's device");
+  TORCH_CHECK(nsplit >= 0, "nsplit must be >= 0");
+  // a forced count beyond the K-steps is legal: empty slices store zeros
+  const int ns = nsplit == 0 ? int(wgrad_nsplit(T, out, in))
+                             : int(std::min<int64_t>(nsplit, 1024));
+  const bool bias = dbp || bias_f32;
+  const auto f32 = dy.options().dtype(torch::kFloat32);
+  auto slab = torch::empty({int64_t(ns), out, in}, f32);
+  Tensor bpart = bias ? torch::empty({int64_t(ns), out}, f32) : Tensor();
+  Tensor bout = (bias && !dbp) ? torch::empty({out}, f32) : Tensor();
+  WgradArgs a;
+  a.dy = bfp(dy); a.x = bfp(x);
+  a.ld_dy = T > 1 ? dy.stride(0) : out;
+  a.ld_x = T > 1 ? x.stride(0) : in;
+  a.T = T; a.out = int(out); a.in = int(in); a.nsplit = ns;
+  a.slab = slab.data_ptr<float>();
+  a.bpart = bias ? bpart.data_ptr<float>() : nullptr;
+  a.dw = bfp_mut(dw);
+  a.db = dbp;
+  a.bout = bout.defined() ? bout.data_ptr<float>() : nullptr;
+  launch_wgrad(a, stream());
+  const hipError_t err = hipGetLastError();
+  TORCH_CHECK(err == hipSuccess, "wgrad launch failed: ",
+              hipGetErrorString(err));
+  return bout;
+}
+
 // ---- merge plane -----------------------------------------------------------
 // What every merge entry point, fp32 or packed, requires of its tables
 // before anything is launched. offsets: an integer [n_segs + 1] table; the
@@ -1374,6 +1455,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("step_control", &step_control);
   m.def("adamw_step_guarded", &adamw_step_guarded);
   m.def("colsum", &colsum, py::arg("x"), py::arg("dst") = py::none());
+  // wgrad.hip: its own submodule (m.wgrad.bias, ...). Accuracy tests:
+  // tests/test_wgrad_gpu.py, bound self-check tests/test_wgrad_cpu.py.
+  py::module_ wg = m.def_submodule("wgrad", "split-K weight gradient");
+  wg.def("bias", &wgrad_bias, py::arg("dy"), py::arg("x"), py::arg("dw"),
+         py::arg("db") = py::none(), py::arg("bias_f32") = false,
+         py::arg("nsplit") = 0);
+  wg.def("supported", &wgrad_supported);
+  wg.def("tile", &wgrad_tile);
+  wg.def("nsplit", &wgrad_nsplit);
   m.def("weighted_merge", &weighted_merge);
   m.def("grad_merge_weights", &grad_merge_weights);
   m.def("weighted_merge_packed", &weighted_merge_packed);

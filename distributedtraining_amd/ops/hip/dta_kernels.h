@@ -380,6 +380,37 @@ void launch_head_loss(const bf16_t* x, const bf16_t* w,
                       int nsplit, float* ws_m, float* ws_s, float* tlogit,
                       float* m_run, float* s_run, hipStream_t s);
 
+// ---- weight-gradient GEMM with the bias sum folded in (wgrad.hip) ----------
+// dw[out,in] = bf16(float(dw) + dy[T,out]^T x[T,in]), split over T. dy and x
+// are row-major with row strides ld_dy/ld_x (elements, % 8 == 0, >= the
+// width) and 16 B aligned bases; out % DTA_WGRAD_BM == 0, in % DTA_WGRAD_BN
+// == 0, T >= 1 arbitrary (a ragged last K-step is zero-padded). slab:
+// [nsplit, out, in] fp32, every element written (no zero-fill). bpart
+// non-null ([nsplit, out] fp32) also sums dy over t: db = bf16(float(db) +
+// sum) where db is non-null, else bout [out] fp32 is stored. dw/db are bf16
+// views of any (2 B) alignment. Results repeat bit for bit.
+constexpr int DTA_WGRAD_BM = 256;  // out per tile
+constexpr int DTA_WGRAD_BN = 128;  // in per tile
+constexpr int DTA_WGRAD_BK = 32;   // rows of t per K-step
+// split count: two resident blocks per CU (512 threads, 54 KB LDS each),
+// every slice owning at least one K-step
+inline int dta_wgrad_nsplit(int64_t T, int64_t out, int64_t in, int cus) {
+  const int64_t tiles = (out / DTA_WGRAD_BM) * (in / DTA_WGRAD_BN);
+  const int64_t ksteps = (T + DTA_WGRAD_BK - 1) / DTA_WGRAD_BK;
+  int64_t ns = 2 * int64_t(cus) / (tiles > 0 ? tiles : 1);
+  if (ns > ksteps) ns = ksteps;
+  return int(ns < 1 ? 1 : ns);
+}
+struct WgradArgs {
+  const bf16_t *dy, *x;
+  int64_t ld_dy, ld_x, T;
+  int out, in, nsplit;
+  float *slab, *bpart;
+  bf16_t *dw, *db;
+  float* bout;
+};
+void launch_wgrad(const WgradArgs& a, hipStream_t s);
+
 // ---- embedding ------------------------------------------------------------
 // pos_p: device position offset for wpe (graph-replayable decode).
 // doc_start: optional int32 [n_tok] (packed sequences, the attention q_lo):

@@ -22,6 +22,7 @@ SRC = [
     "distributedtraining_amd/ops/hip/norms.hip",
     "distributedtraining_amd/ops/hip/ce.hip",
     "distributedtraining_amd/ops/hip/head_loss.hip",
+    "distributedtraining_amd/ops/hip/wgrad.hip",
     "distributedtraining_amd/ops/hip/embedding.hip",
     "distributedtraining_amd/ops/hip/rope.hip",
     "distributedtraining_amd/ops/hip/gemv.hip",

@@ -3,10 +3,12 @@
 
 The dump holds a seeded sample of the flat planes (bench.dump_outputs); this
 maps every sampled element back to its parameter through FlatParams.spec
-and counts, per class (weights incl. wte/wpe, Linear biases, norm γ/β), the
-elements of params.npy and adam_m.npy that differ, the largest difference,
-and how many adam_m differences exceed 0.1 x one bf16 ulp of the gradient
-(adam_m is 0.1 x the bf16 gradient after the dump's single fresh step).
+and counts, per class (Linear weights, wte/wpe, Linear biases, norm γ/β),
+the elements of params.npy and adam_m.npy that differ, the largest
+difference, and how many adam_m differences exceed 0.1 x one bf16 ulp of the
+gradient (adam_m is 0.1 x the bf16 gradient after the dump's single fresh
+step). --offenders also says, per class, how large the gradients of the
+elements beyond one ulp are against the class's rms gradient.
 
     python tools/dump_diff_by_param.py REF_DIR DIR [DIR ...] [--model gpt2-small]
 """
@@ -19,7 +21,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-CLASSES = ("weights, wte, wpe", "Linear biases", "norm γ/β")
+CLASSES = ("Linear weights", "wte, wpe", "Linear biases", "norm γ/β")
 
 
 def classes_of_sample(model_name):
@@ -36,7 +38,10 @@ def classes_of_sample(model_name):
             continue
         seen.add(id(p))
         leaf = name.rsplit(".", 1)[-1]
-        c = 0 if p.dim() >= 2 else (2 if "ln" in leaf or "norm" in leaf else 1)
+        if p.dim() >= 2:
+            c = 1 if leaf in ("wte", "wpe", "embed_tokens") else 0
+        else:
+            c = 3 if "ln" in leaf or "norm" in leaf else 2
         cls.append(torch.full((p.numel(),), c, dtype=torch.int8))
     cls = torch.cat(cls)
     if cls.numel() > bench.DUMP_MAX_ELEMS:
@@ -58,6 +63,8 @@ def main():
     ap.add_argument("ref")
     ap.add_argument("dirs", nargs="+")
     ap.add_argument("--model", default="gpt2-small")
+    ap.add_argument("--offenders", action="store_true",
+                    help="size of the gradients beyond one bf16 ulp")
     a = ap.parse_args()
     cls = classes_of_sample(a.model)
     ref = {n: np.load(os.path.join(a.ref, n + ".npy"))
@@ -75,10 +82,19 @@ def main():
             dm = np.abs(cur["adam_m"][sel] - ref["adam_m"][sel])
             grad = ref["adam_m"][sel] / np.float32(0.1)
             # 1.01: adam_m = fp32(0.1) * g is itself rounded
-            over = int((dm > 0.1 * 1.01 * bf16_ulp(grad)).sum())
+            beyond = dm > 0.1 * 1.01 * bf16_ulp(grad)
+            over = int(beyond.sum())
             print(f"| {d} | {cname} ({int(sel.sum())}) | "
                   f"{int((dp != 0).sum())} / {dp.max(initial=0):.3g} | "
                   f"{int((dm != 0).sum())} / {dm.max(initial=0):.3g} | {over} |")
+            if a.offenders and over:
+                rms = float(np.sqrt(np.mean(grad.astype(np.float64) ** 2)))
+                rel = np.abs(grad[beyond]) / rms
+                ulps = dm[beyond] / (0.1 * bf16_ulp(grad[beyond]))
+                print(f"| {d} | {cname}: |g| / rms |g| of the {over} beyond "
+                      f"one ulp | median {np.median(rel):.3g} | max "
+                      f"{rel.max():.3g} | ulps: median {np.median(ulps):.3g} "
+                      f"max {ulps.max():.3g} |")
         print(f"| {d} | loss abs diff | "
               f"{abs(float(cur['loss'][0] - ref['loss'][0])):.3g} | | |")
 
