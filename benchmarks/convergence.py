@@ -12,9 +12,16 @@ Usage: python benchmarks/convergence.py [--rounds 6] [--miners 4]
        [--steps-per-round 30] [--strategy mean|nesterov|parameterized]
        [--exchange-dtype fp32|bf16|int8|topk] [--topk-k 128]
        [--topk-block 4096] [--topk-error-feedback true|false]
+       [--strategy trimmed_mean|median] [--trim-count 1]
+       [--poison K --poison-kind scale|signflip|nan]
 --exchange-dtype (default fp32: the deltas reach the averager as they are)
 sends every miner's delta through that wire form first; topk keeps one
 error-feedback residual per miner across the rounds.
+--strategy trimmed_mean / median is the coordinate-wise robust merge
+(--trim-count miners dropped per side for trimmed_mean); the JSON then holds
+every round's per-miner outside share. --poison K replaces the deltas of the
+last K miners before the merge: by -20 x delta (scale), -delta (signflip) or
+NaN (nan).
 Prints one JSON line; add --table for a human round-by-round table.
 """
 
@@ -35,7 +42,12 @@ def main() -> int:
     ap.add_argument("--steps-per-round", type=int, default=30)
     ap.add_argument("--strategy", default="mean",
                     choices=["mean", "nesterov", "parameterized",
-                             "score_weighted"])
+                             "score_weighted", "trimmed_mean", "median"])
+    ap.add_argument("--trim-count", type=int, default=1)
+    ap.add_argument("--poison", type=int, default=0,
+                    help="the last K miners send a hostile delta")
+    ap.add_argument("--poison-kind", default="scale",
+                    choices=["scale", "signflip", "nan"])
     ap.add_argument("--tokenizer", default="byte", choices=["byte", "bpe"],
                     help="byte: 258-vocab byte tokenizer; bpe: GPT-2-style "
                          "byte-level BPE trained offline on the corpus "
@@ -49,6 +61,11 @@ def main() -> int:
                     choices=["true", "false"])
     ap.add_argument("--table", action="store_true")
     args = ap.parse_args()
+    robust = args.strategy in ("trimmed_mean", "median")
+    if robust and args.exchange_dtype == "topk":
+        ap.error("the robust merges do not take top-k deltas")
+    if not 0 <= args.poison <= args.miners:
+        ap.error("--poison must be between 0 and --miners")
 
     from distributedtraining_amd.config import (AverageConfig, Config,
                                                 ModelConfig)
@@ -103,7 +120,9 @@ def main() -> int:
     validator = DeltaValidator(base_model, fp, ev, cfg.validate)
     av = ParameterizedAverager(base_model, fp,
                                AverageConfig(strategy=args.strategy,
-                                             meta_epochs=2, meta_lr=0.01))
+                                             meta_epochs=2, meta_lr=0.01,
+                                             trim_count=args.trim_count))
+    outside_shares = []
     losses = [validator.base_loss]
     feedback = args.topk_error_feedback == "true"
     residuals = [None] * args.miners     # topk: what a miner has not sent
@@ -118,6 +137,13 @@ def main() -> int:
                              cfg.train)
             loop.train(args.steps_per_round)
             delta = loop.make_delta().flat.clone()
+            if m >= args.miners - args.poison:
+                if args.poison_kind == "scale":
+                    delta.mul_(-20.0)
+                elif args.poison_kind == "signflip":
+                    delta.neg_()
+                else:
+                    delta.fill_(float("nan"))
             if args.exchange_dtype == "topk":
                 if feedback and residuals[m] is None:
                     residuals[m] = torch.zeros_like(delta)
@@ -138,6 +164,10 @@ def main() -> int:
             merged = av.meta_learning(base, stack, ev)
         elif args.strategy == "nesterov":
             merged = av.nesterov_merge(base, stack)
+        elif robust:
+            merged = av.robust_merge(base, stack)
+            outside_shares.append([round(x, 4)
+                                   for x in av.last_outside_share])
         elif args.strategy == "score_weighted":
             merged = av.score_weighted_merge(base, stack,
                                              [1.0] * args.miners)
@@ -164,6 +194,11 @@ def main() -> int:
     if args.exchange_dtype == "topk":
         out.update(topk_k=args.topk_k, topk_block=args.topk_block,
                    topk_error_feedback=feedback)
+    if robust:
+        out.update(trim_count=args.trim_count,
+                   outside_share=outside_shares)
+    if args.poison:
+        out.update(poison=args.poison, poison_kind=args.poison_kind)
     print(json.dumps(out))
     return 0 if out["improved"] else 1
 

@@ -163,7 +163,13 @@ class AverageConfig:
     # gradient average, θ −= α·ḡ (reference: apply_averaged_gradients,
     # averaging_logic.py:149-153 — default 1e-5, NOT the meta lr)
     gradient_alpha: float = 1e-5
-    strategy: str = "parameterized"  # parameterized | score_weighted | genetic | mean | nesterov
+    # parameterized | score_weighted | genetic | mean | nesterov, or the
+    # Byzantine-robust coordinate-wise merges trimmed_mean | median
+    strategy: str = "parameterized"
+    # trimmed_mean-only: miners dropped per side at every element, clamped to
+    # (N-1)//2 at merge time (N = 1 or 2 degrade to the plain mean). median
+    # always drops (N-1)//2.
+    trim_count: int = 1
     # genetic-only (reference: GeneticAverager, averaging_logic.py:830-970)
     population_size: int = 20
     generations: int = 10

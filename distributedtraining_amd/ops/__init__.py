@@ -39,7 +39,7 @@ __all__ = [
     "cross_entropy_loss", "lm_head_ce", "lm_head_loss",
     "embedding_fwd", "check_q_lo", "check_doc_start", "q_lo_inverse",
     "decode_attention", "rope", "adamw_step", "delta_sub", "axpy_",
-    "weighted_merge",
+    "weighted_merge", "trimmed_merge", "median_trim",
     "grad_merge_weights", "has_nan", "l2norm",
     "grad_sumsq_blocks", "grad_sumsq_partials", "step_control",
     "adamw_step_guarded", "lr_schedule",
@@ -1630,6 +1630,143 @@ def weighted_merge(base: torch.Tensor, deltas,
         acc += W[i].float()[seg] * (base.float() + di)
     out.copy_(acc.to(out.dtype))
     return out
+
+
+# --------------------------------------------------------------------------
+# Robust merge: coordinate-wise trimmed mean / median
+# --------------------------------------------------------------------------
+MERGE_MAX_MODELS = 32    # DTA_MERGE_MAX_MODELS of the kernels
+_KEY_NAN = 0xFFFFFFFF
+_TRIM_CHUNK = 1 << 20    # elements per slice of the CPU path (int64 keys)
+
+
+def median_trim(n: int) -> int:
+    """The ``trim`` that makes :func:`trimmed_merge` a coordinate-wise
+    median: the middle value for odd ``n``, the mean of the two middle
+    values for even ``n``."""
+    return (n - 1) // 2
+
+
+def _order_keys(v: torch.Tensor) -> torch.Tensor:
+    """int64 order keys (values in [0, 2^32)) of an fp32 tensor: the bit
+    pattern with every bit flipped where the sign bit is set and only the
+    sign bit flipped elsewhere, so integer order is
+    -inf < .. < -0.0 < +0.0 < .. < +inf; every NaN is 0xFFFFFFFF."""
+    b = v.contiguous().view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+    key = torch.where(b >= 0x80000000, b ^ 0xFFFFFFFF, b ^ 0x80000000)
+    return torch.where(torch.isnan(v), torch.full_like(key, _KEY_NAN), key)
+
+
+def _key_values(key: torch.Tensor) -> torch.Tensor:
+    """The fp32 values of int64 order keys; the NaN key is 0x7FC00000."""
+    b = torch.where(key >= 0x80000000, key ^ 0x80000000, key ^ 0xFFFFFFFF)
+    b = torch.where(key == _KEY_NAN, torch.full_like(b, 0x7FC00000), b)
+    b = torch.where(b >= 0x80000000, b - (1 << 32), b)   # as signed 32 bit
+    return b.to(torch.int32).view(torch.float32)
+
+
+def _trimmed_merge_cpu(base, rows, trim, out, outside):
+    """The definition. rows(lo, hi) -> [N, hi - lo] fp32 of the deltas."""
+    N = outside.numel()
+    m = torch.tensor(float(N - 2 * trim), dtype=torch.float32)
+    canon = torch.tensor(0x7FC00000, dtype=torch.int32).view(torch.float32)
+    P = base.numel()
+    for lo in range(0, P, _TRIM_CHUNK):
+        hi = min(lo + _TRIM_CHUNK, P)
+        keys = _order_keys(rows(lo, hi))
+        srt, _ = torch.sort(keys, dim=0)
+        vals = _key_values(srt[trim:N - trim])
+        acc = vals[0].clone()            # starts FROM the first kept value
+        for j in range(1, N - 2 * trim):
+            acc = acc + vals[j]
+        o = base[lo:hi] + acc / m
+        # inf - inf has no one NaN across machines: every NaN is 0x7FC00000
+        out[lo:hi] = torch.where(torch.isnan(o), canon, o)
+        outside += ((keys < srt[trim]) | (keys > srt[N - 1 - trim])).sum(dim=1)
+
+
+def trimmed_merge(base: torch.Tensor, deltas, trim: int,
+                  out: Optional[torch.Tensor] = None,
+                  outside: Optional[torch.Tensor] = None):
+    """Coordinate-wise trimmed mean of N deltas on top of ``base``:
+    ``(out fp32 [P], outside int64 [N])``.
+
+    For every element e on its own the N values ``deltas[i, e]`` are put in
+    the total order -inf < .. < -0.0 < +0.0 < .. < +inf < NaN, the ``trim``
+    smallest and the ``trim`` largest are dropped, and the ``m = N - 2 trim``
+    kept ones are summed in ascending order starting from the first of them
+    (plain fp32 adds); ``out[e] = base[e] + sum / m`` with one IEEE division
+    and one add. A NaN result is always 0x7FC00000. ``outside[i]`` counts the
+    elements at which miner i lies strictly outside the kept interval (a tie
+    with its boundary counts for nobody), so it does not depend on the row
+    order; neither does any bit of ``out``. ``trim = median_trim(N)`` is the
+    median; ``trim = 0`` a mean that, unlike ``weighted_merge``, does not
+    depend on the order of the miners. A NaN or an infinity sent by at most
+    ``trim`` miners at an element is trimmed there like any other outlier.
+
+    ``base`` fp32 [P]; ``deltas`` [N, P] fp32 or a PackedDeltas of kind
+    fp32 / bf16 / int8 (dequantised as in ``weighted_merge``), 1 <= N <= 32,
+    0 <= 2 trim < N. A "topk" PackedDeltas is refused: most coordinates are
+    sent by fewer than half of the miners, so a coordinate-wise median would
+    zero almost everything. ``out`` / ``outside``, where given, are
+    overwritten. Both results live on ``base``'s device; the op does not
+    sync. The CPU path is the definition, the GPU kernel equals it bit for
+    bit (hip/merge.hip, trimmed_merge_k)."""
+    if _packed(deltas):
+        if deltas.kind == "topk":
+            raise ValueError(
+                "trimmed_merge: top-k deltas are refused. Most coordinates "
+                "are sent by fewer than half of the miners, so a "
+                "coordinate-wise median would zero almost every element; "
+                "exchange fp32, bf16 or int8 deltas for the robust merge")
+        if deltas.kind == "fp32":
+            deltas = deltas.data
+    if not _packed(deltas) and (deltas.dim() != 2
+                                or deltas.dtype != torch.float32):
+        raise ValueError("trimmed_merge: deltas must be an fp32 [N, P] "
+                         "tensor or a PackedDeltas")
+    N, P = deltas.shape
+    trim = int(trim)
+    if not 1 <= N <= MERGE_MAX_MODELS:
+        raise ValueError(f"trimmed_merge: 1 <= N <= {MERGE_MAX_MODELS}, "
+                         f"got {N}")
+    if trim < 0 or 2 * trim >= N:
+        raise ValueError(f"trimmed_merge: need 0 <= 2 * trim < N, got trim "
+                         f"{trim} for {N} deltas")
+    if base.dtype != torch.float32 or base.dim() != 1 or base.numel() != P:
+        raise ValueError("trimmed_merge: base must be fp32 [P]")
+    if out is None:
+        out = torch.empty_like(base)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (P,):
+        raise ValueError("trimmed_merge: out must be fp32 [P]")
+    if outside is None:
+        outside = torch.zeros(N, dtype=torch.int64, device=base.device)
+    elif outside.dtype != torch.int64 or tuple(outside.shape) != (N,):
+        raise ValueError("trimmed_merge: outside must be int64 [N]")
+    else:
+        outside.zero_()
+    if use_hip(base):
+        if _packed(deltas):
+            data, scales, block = _packed_args(deltas)
+        else:
+            data, scales, block = deltas, base.new_empty(0), 0
+        require_ext().robust.trimmed_merge(base, data, scales, block, trim,
+                                           out, outside)
+        return out, outside
+    if _packed(deltas):
+        if deltas.kind == "bf16":
+            def rows(lo, hi):
+                return deltas.data[:, lo:hi].to(torch.float32)
+        else:
+            full = deltas.dequantize()
+
+            def rows(lo, hi):
+                return full[:, lo:hi]
+    else:
+        def rows(lo, hi):
+            return deltas[:, lo:hi]
+    _trimmed_merge_cpu(base, rows, trim, out, outside)
+    return out, outside
 
 
 def grad_merge_weights(g: torch.Tensor, base: torch.Tensor,

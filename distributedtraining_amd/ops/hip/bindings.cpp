@@ -827,6 +827,60 @@ void axpy_packed(Tensor w, Tensor data, Tensor scales, int64_t block,
                      stream());
 }
 
+// ---- robust merge (merge.hip, trimmed_merge_k) -------------------------------
+int trimmed_kind(const Tensor& data) {
+  switch (data.scalar_type()) {
+    case torch::kFloat32: return DELTA_F32;
+    case torch::kBFloat16: return DELTA_BF16;
+    case torch::kInt8: return DELTA_I8;
+    default:
+      TORCH_CHECK(false, "trimmed_merge: deltas must be fp32, bf16 or int8 "
+                         "(top-k deltas have no coordinate-wise median)");
+  }
+}
+// data [N, P] fp32 (scales empty, block unused), or bf16 / int8 + scales as
+// the packed merge takes them. out [P] fp32 is written; outside, where given,
+// is an int64 [N] tensor the counts are ADDED to (the caller zero-fills it).
+void trimmed_merge(Tensor base, Tensor data, Tensor scales, int64_t block,
+                   int64_t trim, Tensor out, OptTensor outside) {
+  const int64_t P = base.numel();
+  TORCH_CHECK(data.dim() == 2, "trimmed_merge: deltas must be [N, cols]");
+  const int n_models = merge_n_models(data.size(0));
+  TORCH_CHECK(trim >= 0 && 2 * trim < n_models,
+              "trimmed_merge: need 0 <= 2 * trim < n_models, got trim ", trim,
+              " for ", n_models, " deltas");
+  const int kind = trimmed_kind(data);
+  check_plane_f32(base, P, "base"); check_plane_f32(out, P, "out");
+  PackedView d;
+  if (kind == DELTA_F32) {
+    check_deltas_f32(data, P);
+    d = PackedView{data.data_ptr(), nullptr, P, 0, 0, DELTA_F32};
+  } else {
+    d = packed_view(data, scales, P, block);
+  }
+  if (dta_trimmed_vec(kind, n_models, P) == 4)
+    TORCH_CHECK(aligned16(base) && aligned16(out) && aligned16(data),
+                "trimmed_merge: base, out and the deltas must be 16-byte "
+                "aligned");
+  int64_t* cnt = nullptr;
+  if (outside.has_value() && outside->defined()) {
+    TORCH_CHECK(outside->is_cuda() && outside->is_contiguous() &&
+                    outside->scalar_type() == torch::kInt64 &&
+                    outside->dim() == 1 && outside->numel() == n_models,
+                "outside must be a contiguous int64 [N] GPU tensor");
+    cnt = outside->data_ptr<int64_t>();
+  }
+  launch_trimmed_merge(base.data_ptr<float>(), d, n_models, int(trim), P,
+                       out.data_ptr<float>(), cnt, stream());
+}
+// elements one sweep of the launcher's capped grid covers (tests size a case
+// that takes the grid-stride loop round a second time from it)
+int64_t trimmed_sweep(Tensor data, int64_t P) {
+  TORCH_CHECK(data.dim() == 2, "trimmed_merge: deltas must be [N, cols]");
+  return dta_trimmed_sweep(trimmed_kind(data), merge_n_models(data.size(0)),
+                           P);
+}
+
 // (codes [nb*block] int8, scales [nb] fp32) of x - base, or of x when base
 // is empty. topk_k > 0: the top-k form of the same delta instead, {entries
 // [nb*topk_k] int32} of (x - base) + residual_in, with the remainder
@@ -1464,6 +1518,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   wg.def("supported", &wgrad_supported);
   wg.def("tile", &wgrad_tile);
   wg.def("nsplit", &wgrad_nsplit);
+  // trimmed_merge_k: its own submodule as well. CPU definition:
+  // ops.trimmed_merge; tests/test_robust_merge_gpu.py holds the kernel to it
+  // bit for bit.
+  py::module_ rb = m.def_submodule("robust", "trimmed-mean / median merge");
+  rb.def("trimmed_merge", &trimmed_merge, py::arg("base"), py::arg("data"),
+         py::arg("scales"), py::arg("block"), py::arg("trim"), py::arg("out"),
+         py::arg("outside") = py::none());
+  rb.def("sweep", &trimmed_sweep);
   m.def("weighted_merge", &weighted_merge);
   m.def("grad_merge_weights", &grad_merge_weights);
   m.def("weighted_merge_packed", &weighted_merge_packed);

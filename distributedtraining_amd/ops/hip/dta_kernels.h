@@ -192,6 +192,31 @@ void launch_grad_merge_weights_packed(const void* g, bool g_is_bf16,
                                       const int64_t* chunks, int n_models,
                                       int n_chunks, int64_t P, float* grad_w,
                                       int n_segs, hipStream_t s);
+// Robust merge: out[e] = base[e] + mean of the sorted positions trim ..
+// n_models-1-trim of the n_models values delta_i[e] (0 <= 2*trim < n_models;
+// trim = (n_models-1)/2 is the median), and outside[i] += the number of
+// elements at which row i lies strictly outside that kept interval. The
+// order is total: -inf < .. < -0 < +0 < .. < +inf < NaN. d: fp32 (kind
+// DELTA_F32, data [N, ld = P]), bf16 or int8. Bit-equal to the CPU path of
+// ops.trimmed_merge, independent of the row order. outside: int64
+// [n_models], zero-filled by the caller, integer atomics only; null: no
+// counts. The rows are padded to dta_trimmed_pad(n_models) sort keys per
+// element; dta_trimmed_vec elements per lane: where that is 4, base and out
+// must be 16 B aligned and data 16 B (fp32), 8 B (bf16) or 4 B (int8).
+inline int dta_trimmed_pad(int n_models) {
+  return n_models <= 4 ? 4 : n_models <= 8 ? 8 : n_models <= 16 ? 16 : 32;
+}
+inline int dta_trimmed_vec(int kind, int n_models, int64_t P) {
+  // 32 keys, their sorted copy and 32 counters per ELEMENT: one per lane
+  if (dta_trimmed_pad(n_models) == 32) return 1;
+  // as the packed merge: a row start must be aligned, int8 rows are padded
+  return (kind == DELTA_I8 || P % 4 == 0) ? 4 : 1;
+}
+void launch_trimmed_merge(const float* base, const PackedView& d,
+                          int n_models, int trim, int64_t P, float* out,
+                          int64_t* outside, hipStream_t s);
+// elements one sweep of its capped grid covers; more take the grid-stride loop
+int64_t dta_trimmed_sweep(int kind, int n_models, int64_t P);
 // w += alpha * row `row` of d, dequantised in registers
 void launch_axpy_packed(float* w, const PackedView& d, int row, float alpha,
                         int64_t P, hipStream_t s);

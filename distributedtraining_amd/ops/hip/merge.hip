@@ -28,6 +28,8 @@
 #include "dta_common.h"
 #include "dta_kernels.h"
 
+#include <utility>
+
 namespace {
 
 constexpr int MAX_SEGS = 1024;   // parameter tensors per model (GPT-2: 75)
@@ -105,6 +107,64 @@ DEV void delta_at(const PackedView& d, int i, int64_t e, float (&out)[V]) {
   }
 }
 
+// delta_at in two halves, for a kernel that issues the loads of many rows
+// before it uses any of them: delta_raw only loads (the words as they are
+// stored, and the scale for int8), raw_value turns element k of the vector
+// into the fp32 value delta_at gives. With the conversion next to the load,
+// inside a branch per row, every row's load was waited for before the next
+// was issued (the robust merge ran 2 to 3 times longer on bf16 and int8).
+// Alignment and bounds as for delta_at; bf16 with V == 1 is the 2 B load.
+typedef __attribute__((ext_vector_type(2))) uint32_t u32x2;
+template <int KIND, int V> constexpr int raw_words() {
+  return KIND == DELTA_F32 ? V : (KIND == DELTA_BF16 && V == 4) ? 2 : 1;
+}
+template <int KIND, int V>
+DEV void delta_raw(const PackedView& d, int i, int64_t e,
+                   uint32_t (&raw)[raw_words<KIND, V>()], float& sc) {
+  static_assert(V == 1 || V == 4, "one element or one vector");
+  if constexpr (KIND == DELTA_F32) {
+    const float* p = static_cast<const float*>(d.data) + int64_t(i) * d.ld + e;
+#pragma unroll
+    for (int k = 0; k < V; ++k) raw[k] = __float_as_uint(p[k]);
+  } else if constexpr (KIND == DELTA_BF16) {
+    const ushort* p =
+        static_cast<const ushort*>(d.data) + int64_t(i) * d.ld + e;
+    if constexpr (V == 4) {
+      const u32x2 v = *reinterpret_cast<const u32x2*>(p);
+      raw[0] = v[0];
+      raw[1] = v[1];
+    } else {
+      raw[0] = p[0];
+    }
+  } else {
+    const signed char* p =
+        static_cast<const signed char*>(d.data) + int64_t(i) * d.ld + e;
+    sc = d.scales[int64_t(i) * d.nb + (e >> d.shift)];
+    raw[0] = *reinterpret_cast<const uint32_t*>(V == 4 ? p : p - (e & 3));
+  }
+}
+template <int KIND, int V>
+DEV float raw_value(const uint32_t (&raw)[raw_words<KIND, V>()], float sc,
+                    int k, int64_t e) {
+  if constexpr (KIND == DELTA_F32) {
+    return __uint_as_float(raw[k]);
+  } else if constexpr (KIND == DELTA_BF16) {
+    if constexpr (V == 4)
+      return bf2f(ushort(raw[k >> 1] >> (16 * (k & 1))));
+    else
+      return bf2f(ushort(raw[0]));
+  } else {
+    const int b = V == 4 ? k : int(e & 3);
+    return mul_rn(float(int(raw[0] << (24 - 8 * b)) >> 24), sc);
+  }
+}
+// raw words and scale whose every element is a NaN
+template <int KIND> DEV void raw_nan(uint32_t& word, float& sc) {
+  word = KIND == DELTA_F32 ? 0x7FC00000u : KIND == DELTA_BF16 ? 0x7FC07FC0u
+                                                               : 0u;
+  sc = __uint_as_float(0x7FC00000u);
+}
+
 // The kernels take the view as plain parameters, so the two pointers keep
 // __restrict__, and rebuild it first thing.
 #define DELTA_PARAMS                                                        \
@@ -172,6 +232,212 @@ __global__ void weighted_merge_k(const float* __restrict__ base,
       for (int k = 0; k < V; ++k)
         if (k < n) out[e + k] = acc[k];
     }
+  }
+}
+
+// ---- robust merge: coordinate-wise trimmed mean / median ---------------------
+// out[e] = base[e] + mean of the values at sorted positions t .. N-1-t of
+// delta_0[e] .. delta_{N-1}[e]; outside[i] counts the elements at which
+// miner i lies strictly outside that kept interval. The definition is the
+// CPU path of ops.trimmed_merge and the kernel equals it bit for bit: the
+// order is taken on integer keys, the kept values are summed in ascending
+// position from the first one, then one IEEE division and one add.
+//
+// order key of a float: flip every bit of a negative, the sign bit of the
+// rest, so unsigned order is -inf < .. < -0 < +0 < .. < +inf; every NaN is
+// 0xFFFFFFFF, above all of them. The pad rows N .. NP-1 get that key too:
+// equal keys are the same value, so positions 0 .. N-1 of the sorted NP
+// hold the sorted N whatever a tie with a pad did.
+constexpr uint32_t KEY_NAN = 0xFFFFFFFFu;
+
+DEV uint32_t order_key(float v) {
+  const uint32_t b = __float_as_uint(v);
+  if ((b & 0x7FFFFFFFu) > 0x7F800000u) return KEY_NAN;
+  return (b & 0x80000000u) ? ~b : (b ^ 0x80000000u);
+}
+// KEY_NAN comes back as the NaN 0x7FFFFFFF; the kernel makes every NaN it
+// stores 0x7FC00000
+DEV float key_value(uint32_t k) {
+  return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k);
+}
+
+// Batcher's odd-even merge sort of NP keys as a list of comparators, built
+// at compile time: 5 / 19 / 63 / 191 for NP = 4 / 8 / 16 / 32.
+template <int NP>
+struct SortNet {
+  int n;
+  unsigned char lo[NP * 6], hi[NP * 6];
+};
+template <int NP>
+constexpr SortNet<NP> make_sort_net() {
+  SortNet<NP> net{};
+  for (int p = 1; p < NP; p <<= 1)
+    for (int k = p; k >= 1; k >>= 1)
+      for (int j = k % p; j + k < NP; j += 2 * k)
+        for (int i = 0; i < k && i + j + k < NP; ++i)
+          if ((i + j) / (2 * p) == (i + j + k) / (2 * p)) {
+            net.lo[net.n] = (unsigned char)(i + j);
+            net.hi[net.n] = (unsigned char)(i + j + k);
+            ++net.n;
+          }
+  return net;
+}
+template <int NP> constexpr int sort_net_size() {
+  return NP == 4 ? 5 : NP == 8 ? 19 : NP == 16 ? 63 : 191;
+}
+// every index below is a constant expression: the keys stay in registers
+// (a runtime-indexed array would go to scratch)
+template <int NP, int A, int B>
+DEV void compare_exchange(uint32_t (&s)[NP]) {
+  const uint32_t a = s[A], b = s[B];
+  s[A] = a < b ? a : b;
+  s[B] = a < b ? b : a;
+}
+template <int NP, int... C>
+DEV void sort_keys(uint32_t (&s)[NP], std::integer_sequence<int, C...>) {
+  constexpr SortNet<NP> net = make_sort_net<NP>();
+  static_assert(net.n == sizeof...(C), "comparator count");
+  (compare_exchange<NP, net.lo[C], net.hi[C]>(s), ...);
+}
+
+constexpr int TRIM_THREADS = 256;
+constexpr int TRIM_WAVES = TRIM_THREADS / WAVE;
+
+// One pass over P, V elements per lane and iteration as in weighted_merge_k.
+// The N loads of a vector are issued (delta_raw) before any is converted or
+// sorted, so they are in flight together. n_models and trim are runtime:
+// rows past n_models are pads, and the kept range is taken with masks over
+// the unrolled positions. A lane holds the vectors of the NP rows as they
+// were stored and, per element, the NP keys twice: as they came (for the
+// counts) and sorted. cnt[] lives across the grid-stride loop; at the end it
+// is folded per wave, through LDS per block, and one 64-bit integer
+// atomicAdd per (block, miner) goes into outside (zero-filled by the caller;
+// null: no counts). No barrier in the loop and no return before the one
+// after it. Every instantiation the launcher uses has no scratch and no
+// spill (docs/kernels.md); <32, 4> would not fit 256 vector registers, so
+// 32 rows take one element per lane.
+template <int KIND, int NP, int V>
+__global__ void __launch_bounds__(TRIM_THREADS)
+trimmed_merge_k(const float* __restrict__ base, DELTA_PARAMS, int n_models,
+                int trim, int64_t P, float* __restrict__ out,
+                unsigned long long* __restrict__ outside) {
+  __shared__ uint32_t s_cnt[TRIM_WAVES][NP];
+  uint32_t cnt[NP];
+#pragma unroll
+  for (int i = 0; i < NP; ++i) cnt[i] = 0;
+  const float fm = float(n_models - 2 * trim);   // kept values, >= 1
+
+  int64_t e = (int64_t(blockIdx.x) * blockDim.x + threadIdx.x) * V;
+  const int64_t stride = int64_t(gridDim.x) * blockDim.x * V;
+  for (; e < P; e += stride) {
+    const int n = (V == 1 || e + V <= P) ? V : int(P - e);
+    // The row stride and the row count are re-read through an empty asm in
+    // every trip. Left loop-invariant, the NP row pointers (and NP scale
+    // pointers for int8) and a lane mask per row (i < n_models) are hoisted
+    // out of the loop into scalar registers, which NP = 16 and 32 do not
+    // have: the resource report showed hundreds of spilled SGPRs. Formed
+    // next to their use they cost a few scalar instructions.
+    int64_t ld = dl_ld, nb = dl_nb;
+    int rows = n_models;
+    asm volatile("" : "+s"(ld), "+s"(nb), "+s"(rows));
+    const PackedView deltas{dl_data, dl_scales, ld, nb, dl_shift, KIND};
+    constexpr int RW = raw_words<KIND, V>();
+    uint32_t raw[NP][RW];
+    float sc[NP];
+#pragma unroll
+    for (int i = 0; i < NP; ++i) {
+      // a pad row stays NaN, the key above every real one
+#pragma unroll
+      for (int w = 0; w < RW; ++w) raw_nan<KIND>(raw[i][w], sc[i]);
+      if (i < rows) delta_raw<KIND, V>(deltas, i, e, raw[i], sc[i]);
+    }
+    float b[V], r[V];
+    if (V == 4 && n == 4) {
+      const f32x4 vb = *reinterpret_cast<const f32x4*>(base + e);
+#pragma unroll
+      for (int k = 0; k < V; ++k) b[k] = vb[k];
+    } else {
+#pragma unroll
+      for (int k = 0; k < V; ++k) b[k] = k < n ? base[e + k] : 0.f;
+    }
+    // likewise the words made of the kept range below, three per position:
+    // they are formed after the loads. With V == 4 they serve four elements
+    // and stay live across four sorts; 3 * 16 of them no longer fit the
+    // scalar file (18 to 22 spilled SGPRs), so that instantiation makes them
+    // in vector registers, which it has to spare.
+    int first = trim, last = n_models - 1 - trim;   // kept positions
+    if constexpr (V == 4 && NP >= 16)
+      asm volatile("" : "+v"(first), "+v"(last));
+    else
+      asm volatile("" : "+s"(first), "+s"(last));
+#pragma unroll
+    for (int k = 0; k < V; ++k) {
+      // the keys of element k as the rows came (for the counts) and sorted
+      uint32_t key[NP], s[NP];
+#pragma unroll
+      for (int i = 0; i < NP; ++i)
+        s[i] = key[i] = order_key(raw_value<KIND, V>(raw[i], sc[i], k, e));
+      sort_keys<NP>(s, std::make_integer_sequence<int, sort_net_size<NP>()>{});
+      // kept: all ones at a kept position, one 32-bit word (a select per
+      // position holds a 64-bit lane mask each instead). The sorted keys
+      // ascend, so the interval's ends are a min and a max under the mask.
+      // The sum starts at -0.0, the one float with -0.0 + x == x in bits for
+      // every x, and a position that is not kept adds -0.0: the same bits as
+      // starting FROM the first kept value, so a kept -0.0 alone stays -0.0.
+      uint32_t klo = KEY_NAN, khi = 0;
+      float sum = -0.f;
+      {
+#pragma clang fp contract(off)
+#pragma unroll
+        for (int j = 0; j < NP; ++j) {
+          // first <= j <= last iff (j - first) | (last - j) has no sign bit
+          const int x = (j - first) | (last - j);
+          const uint32_t kept = ~uint32_t(x >> 31);
+          const uint32_t lo_j = s[j] | ~kept, hi_j = s[j] & kept;
+          klo = lo_j < klo ? lo_j : klo;
+          khi = hi_j > khi ? hi_j : khi;
+          const uint32_t term = (__float_as_uint(key_value(s[j])) & kept) |
+                                (uint32_t(x) & 0x80000000u);
+          sum = sum + __uint_as_float(term);
+        }
+        const float mean = __fdiv_rn(sum, fm);
+        const float o = b[k] + mean;
+        // inf - inf has no one NaN: every NaN leaves as 0x7FC00000
+        r[k] = o != o ? __uint_as_float(0x7FC00000u) : o;
+      }
+      if (k < n) {
+        // key outside [klo, khi], as one unsigned compare
+        const uint32_t span = khi - klo;
+#pragma unroll
+        for (int i = 0; i < NP; ++i)
+          cnt[i] += (key[i] - klo > span) ? 1u : 0u;
+      }
+    }
+    if (V == 4 && n == 4) {
+      *reinterpret_cast<f32x4*>(out + e) = f32x4{r[0], r[1], r[2], r[3]};
+    } else {
+#pragma unroll
+      for (int k = 0; k < V; ++k)
+        if (k < n) out[e + k] = r[k];
+    }
+  }
+
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  if (outside != nullptr) {
+#pragma unroll
+    for (int i = 0; i < NP; ++i) {
+      uint32_t c = cnt[i];
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) c += uint32_t(__shfl_xor(int(c), o));
+      if (lane == 0) s_cnt[wid][i] = c;
+    }
+  }
+  __syncthreads();
+  if (outside != nullptr && int(threadIdx.x) < n_models) {
+    unsigned long long tot = 0;
+#pragma unroll
+    for (int w = 0; w < TRIM_WAVES; ++w) tot += s_cnt[w][threadIdx.x];
+    if (tot != 0) atomicAdd(outside + threadIdx.x, tot);
   }
 }
 
@@ -756,6 +1022,43 @@ void launch_weighted_merge_packed(const float* base, const PackedView& d,
   else if (v4) MERGE_GO(DELTA_BF16, 4);
   else MERGE_GO(DELTA_BF16, 1);
 #undef MERGE_GO
+}
+
+int64_t dta_trimmed_sweep(int kind, int n_models, int64_t P) {
+  return int64_t(MAX_RESIDENT_BLOCKS) * TRIM_THREADS *
+         dta_trimmed_vec(kind, n_models, P);
+}
+
+void launch_trimmed_merge(const float* base, const PackedView& d,
+                          int n_models, int trim, int64_t P, float* out,
+                          int64_t* outside, hipStream_t s) {
+  const int np = dta_trimmed_pad(n_models);
+  const int v = dta_trimmed_vec(d.kind, n_models, P);
+  const int grid = elementwise_grid(P, TRIM_THREADS, v);
+  auto* cnt = reinterpret_cast<unsigned long long*>(outside);
+#define TRIM_GO(KIND, NP, V)                                                \
+  trimmed_merge_k<KIND, NP, V><<<grid, TRIM_THREADS, 0, s>>>(               \
+      base, DELTA_ARGS(d), n_models, trim, P, out, cnt)
+#define TRIM_NP(KIND, V)                                                    \
+  do {                                                                      \
+    if (np == 4) TRIM_GO(KIND, 4, V);                                       \
+    else if (np == 8) TRIM_GO(KIND, 8, V);                                  \
+    else TRIM_GO(KIND, 16, V);                                              \
+  } while (0)
+  // 32 keys are one element per lane (dta_trimmed_vec): <32, 4> would need
+  // more than the 256 vector registers and is not built
+#define TRIM_KIND(KIND)                                                     \
+  do {                                                                      \
+    if (np == 32) TRIM_GO(KIND, 32, 1);                                     \
+    else if (v == 4) TRIM_NP(KIND, 4);                                      \
+    else TRIM_NP(KIND, 1);                                                  \
+  } while (0)
+  if (d.kind == DELTA_I8) TRIM_KIND(DELTA_I8);
+  else if (d.kind == DELTA_BF16) TRIM_KIND(DELTA_BF16);
+  else TRIM_KIND(DELTA_F32);
+#undef TRIM_KIND
+#undef TRIM_NP
+#undef TRIM_GO
 }
 
 void launch_grad_merge_weights(const void* g, bool g_is_bf16,

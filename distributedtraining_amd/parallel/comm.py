@@ -139,6 +139,7 @@ class PackedDeltas:
     ``ops.weighted_merge``, ``ops.grad_merge_weights`` and ``ops.axpy_``
     take the container where they take an [N, P] tensor and dequantise in
     registers; their results equal the tensor path on :meth:`dequantize`.
+    ``ops.trimmed_merge`` does the same for every kind but "topk".
     """
 
     kind: str

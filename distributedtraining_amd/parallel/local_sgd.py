@@ -11,7 +11,8 @@ Collective choice per strategy (see merge_round): mean/nesterov use an
 all-reduce (O(P) resident — mandatory at Llama scale); score-weighted,
 meta-learned and genetic use an all-gather (every delta HBM-resident,
 optionally bf16/int8/top-k on the wire, and with comm.resident_dtype =
-"wire" also in that form in HBM). Deterministic merges are computed
+"wire" also in that form in HBM); so do the robust trimmed_mean / median
+merges, which need every delta (top-k excluded). Deterministic merges are computed
 redundantly by every rank (identical bases, no broadcast); the
 meta-learned and genetic merges run on rank 0 (they need val-loss
 evaluations) and are broadcast (C2/C5).
@@ -61,6 +62,12 @@ class LocalSGDNode:
         self.residual: Optional[torch.Tensor] = None
         if self._topk():
             check_topk_format(cfg.comm.topk_k, cfg.comm.topk_block)
+            if self.merge_strategy in ("trimmed_mean", "median"):
+                raise ValueError(
+                    f"merge strategy {self.merge_strategy!r} cannot run on "
+                    "comm.exchange_dtype = 'topk': most coordinates are sent "
+                    "by fewer than half of the miners, so a coordinate-wise "
+                    "median would zero almost everything")
 
     def _topk(self) -> bool:
         return self.cfg.comm.exchange_dtype == "topk"
@@ -143,7 +150,9 @@ class LocalSGDNode:
         * score_weighted/parameterized/genetic: all-gather, all deltas
           HBM-resident (8 fp32 GPT-2 deltas ≈ 4 GB — the scoring/meta/
           evolutionary paths need every delta individually); with
-          comm.resident_dtype = "wire" they stay bf16/int8 in HBM."""
+          comm.resident_dtype = "wire" they stay bf16/int8 in HBM;
+        * trimmed_mean/median: the same gather, then the coordinate-wise
+          robust merge on every rank."""
         base = self.miner.base
         strat = self.merge_strategy
         if strat in ("mean", "uniform", "nesterov"):
@@ -158,6 +167,14 @@ class LocalSGDNode:
             merged = self.averager.score_weighted_merge(
                 base, self._gather_deltas(self._local_delta(base), base),
                 scores)
+        elif strat in ("trimmed_mean", "median"):
+            # needs every delta, so the gather path (wire dtype and resident
+            # form apply). Bit-identical on every rank whatever the gather
+            # order: computed redundantly, no broadcast
+            deltas = self._gather_deltas(self._local_delta(base), base)
+            merged = self.averager.robust_merge(
+                base, deltas,
+                self.averager.robust_trim(deltas.shape[0], strat))
         elif strat in ("parameterized", "genetic"):
             # both need val-loss evaluations: run on rank 0, broadcast
             deltas = self._gather_deltas(self._local_delta(base), base)

@@ -14,6 +14,11 @@ Reimplements the reference's averaging strategies
 * ``GeneticAverager`` (:830-970) — evolutionary search over per-miner
   weight vectors: fitness = −val loss, top-half survival, Gaussian mutation.
 
+* ``robust_merge`` (beyond parity) — coordinate-wise trimmed mean / median
+  (strategies ``trimmed_mean`` / ``median``): every merge above is a weighted
+  sum, so one hostile delta moves every coordinate of the next base; here up
+  to ``trim`` outliers per element, NaN and infinities included, are dropped.
+
 MI355X-native: all N deltas are HBM-resident [N, P] (288 GB per GPU), merge
 is one fused multi-source kernel, grad_W one fused segmented-dot kernel —
 the reference re-loads every model from disk *per batch* (:450-470,
@@ -48,6 +53,9 @@ class ParameterizedAverager:
         self.registry = registry
         self.weights: Optional[torch.Tensor] = None  # W [N, S]
         self.outer_m: Optional[torch.Tensor] = None  # nesterov momentum
+        # robust_merge: per delta, the share of the P elements at which it lay
+        # outside the kept interval (run_round: keyed by hotkey)
+        self.last_outside_share = []
 
     # -- delta collection (reference :365-420) -------------------------------
     def collect_deltas(self) -> Tuple[torch.Tensor, List[str]]:
@@ -215,6 +223,41 @@ class ParameterizedAverager:
         self.outer_m.mul_(mu).add_(d_avg)
         return base + lr * (mu * self.outer_m + d_avg)
 
+    # -- Byzantine-robust strategies (beyond parity) --------------------------
+    def robust_trim(self, n: int, strategy: Optional[str] = None) -> int:
+        """Values dropped per side among ``n`` deltas: the median's
+        (n-1)//2 under strategy "median", else cfg.trim_count clamped to
+        it."""
+        strategy = self.cfg.strategy if strategy is None else strategy
+        most = ops.median_trim(n)
+        if strategy == "median":
+            return most
+        return max(0, min(int(self.cfg.trim_count), most))
+
+    def robust_merge(self, base: torch.Tensor, deltas,
+                     trim: Optional[int] = None) -> torch.Tensor:
+        """base + coordinate-wise trimmed mean of the deltas
+        (ops.trimmed_merge; ``trim`` None: robust_trim). Keeps
+        ``last_outside_share``: per delta, the share of the P elements at
+        which it lay strictly outside the kept interval — near 2·trim/N
+        for an honest miner among honest ones, near 1 for one that is
+        scaled, sign-flipped or NaN. Scores, registry weights and the
+        blacklist are not touched."""
+        n = deltas.shape[0]
+        if n == 0:
+            self.last_outside_share = []
+            return base.clone()
+        if trim is None:
+            trim = self.robust_trim(n)
+        merged, outside = ops.trimmed_merge(base, deltas, trim)
+        # the one host read of the round, for the log; divided on the host
+        # so the share is the same number whichever device counted
+        P = max(base.numel(), 1)
+        self.last_outside_share = [c / P for c in outside.tolist()]
+        log.info("robust merge: N=%d trim=%d outside share %s", n, trim,
+                 ["%.3f" % x for x in self.last_outside_share])
+        return merged
+
     # -- full round (reference run_periodic_averaging :544-583) ---------------
     def run_round(self, val_batches: List[dict]) -> torch.Tensor:
         """Collect deltas, merge per configured strategy, install + publish
@@ -235,6 +278,10 @@ class ParameterizedAverager:
                       if deltas.shape[0] else base.clone())
         elif self.cfg.strategy == "nesterov":
             merged = self.nesterov_merge(base, deltas)
+        elif self.cfg.strategy in ("trimmed_mean", "median"):
+            merged = self.robust_merge(base, deltas)
+            self.last_outside_share = dict(zip(active,
+                                               self.last_outside_share))
         else:
             raise ValueError(f"unknown strategy {self.cfg.strategy!r}")
         self.fp.load_flat_master(merged)
