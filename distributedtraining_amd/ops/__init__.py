@@ -15,7 +15,11 @@ memory-bound is ours. One GEMM class is ours as well: the weight gradients
 ``dW += dyᵀ·x`` of the shapes ``_wgrad_wins`` lists run on the split-K MFMA
 kernel of hip/wgrad.hip, which sums the bias gradient in the same pass over
 ``dy``; every other weight gradient is a library GEMM accumulated directly
-into the flat plane, with the colsum kernel for its bias.
+into the flat plane, with the colsum kernel for its bias. The forward
+projections ``y = x·Wᵀ (+ b)`` can run on the MFMA kernel of hip/gemm.hip,
+which applies the bias, and for the MLP's fc the GELU, to its accumulators
+(``gemm_route`` / ``DTA_GEMM``): "1" wherever its shape contract holds, by
+default only at the ``(T, N, K, epilogue)`` entries of ``_GEMM_WINS``.
 
 Reference behavior being reimplemented: the implicit per-step op set of
 GPT-2 training in /root/reference.
@@ -45,7 +49,7 @@ __all__ = [
     "adamw_step_guarded", "lr_schedule",
     "quantize_blockwise_int8", "dequantize_blockwise_int8",
     "topk_compress_blockwise",
-    "dropout", "rng_tick",
+    "dropout", "rng_tick", "wgrad_route", "gemm_route",
 ]
 
 
@@ -102,6 +106,49 @@ def _wgrad_accum(m, dy2, x2, wgrad, bgrad, want_bias):
     return True, (db32 if want_bias and bgrad is None else None)
 
 
+# Forward-projection routing: "0" library GEMM (addmm / mm, and gelu_fwd for
+# the MLP) everywhere, "1" the kernel of hip/gemm.hip wherever its shape
+# contract holds, anything else: the kernel only at the entries of _GEMM_WINS.
+_GEMM = _os.environ.get("DTA_GEMM", "auto")
+if _GEMM not in ("0", "1"):
+    _GEMM = "auto"
+
+
+def gemm_route(mode: str) -> str:
+    """Switch the forward-projection routing ("0", "1" or "auto"; tests flip
+    it in one process). Returns the previous setting."""
+    global _GEMM
+    if mode not in ("0", "1", "auto"):
+        raise ValueError(f"gemm_route: {mode!r}")
+    prev, _GEMM = _GEMM, mode
+    return prev
+
+
+# (T, N, K, epilogue) at which tools/gemm_ab.py measured the gemm kernel
+# faster than the library arm (addmm, + gelu_fwd for "bias_gelu") by more than
+# that arm's own spread (MI355X, profiles/r12_gemm_fwd.md). Unmeasured shapes
+# stay on the library.
+_GEMM_WINS: frozenset = frozenset()
+
+
+def _gemm_fwd(m, x2, w, b, epi):
+    """The routed forward projection, or None where it stays on the library.
+    epi "bias" without a bias is the plain product."""
+    if _GEMM == "0" or x2.dtype != torch.bfloat16:
+        return None
+    if b is None:
+        epi = "none"
+    if _GEMM == "auto" and (x2.shape[0], w.shape[0], w.shape[1],
+                            epi) not in _GEMM_WINS:
+        return None
+    if w.dtype != x2.dtype or (b is not None and not (
+            b.dtype == x2.dtype and b.is_contiguous())):
+        return None
+    if not m.gemm.supported(x2, w):
+        return None
+    return m.gemm.fwd(x2, w, b, epi)
+
+
 class _LinearFn(torch.autograd.Function):
     """F.linear semantics with two backward optimizations:
 
@@ -119,7 +166,9 @@ class _LinearFn(torch.autograd.Function):
         ctx.xshape = x.shape
         ctx.wgrad = getattr(w, "main_grad", None)
         ctx.bgrad = getattr(b, "main_grad", None) if b is not None else None
-        y = torch.addmm(b, x2, w.t()) if b is not None else x2.mm(w.t())
+        y = _gemm_fwd(require_ext(), x2, w, b, "bias")
+        if y is None:
+            y = torch.addmm(b, x2, w.t()) if b is not None else x2.mm(w.t())
         return y.view(*x.shape[:-1], w.shape[0])
 
     @staticmethod
@@ -160,7 +209,8 @@ class _LinearFn(torch.autograd.Function):
 
 def linear(x: torch.Tensor, w: torch.Tensor,
            b: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """y = x @ w.T (+ b). hipBLASLt GEMM with fused bias epilogue forward;
+    """y = x @ w.T (+ b). hipBLASLt GEMM with fused bias epilogue forward, or
+    the MFMA kernel of hip/gemm.hip where gemm_route sends the shape;
     backward: dgrad by the library; dW and the bias gradient accumulated into
     the flat-grad plane by the wgrad kernel (hip/wgrad.hip) at the shapes of
     _wgrad_wins, else by a library GEMM (beta = 1) + colsum (DTA_LT_BGRADB=1:
@@ -275,9 +325,15 @@ class _MLPGeluFn(torch.autograd.Function):
     def forward(ctx, x, w1, b1, w2, b2):
         m = require_ext()
         x2 = x.reshape(-1, x.shape[-1])
-        pre = torch.addmm(b1, x2, w1.t())
-        h = m.gelu_fwd(pre)
-        y = torch.addmm(b2, h, w2.t())
+        fc = _gemm_fwd(m, x2, w1, b1, "bias_gelu")
+        if fc is None:
+            pre = torch.addmm(b1, x2, w1.t())
+            h = m.gelu_fwd(pre)
+        else:               # bias and GELU on the accumulators: h is
+            pre, h = fc     # gelu_fwd(pre) bit for bit
+        y = _gemm_fwd(m, h, w2, b2, "bias")
+        if y is None:
+            y = torch.addmm(b2, h, w2.t())
         ctx.save_for_backward(x2, w1, w2, pre, h)
         ctx.xshape = x.shape
         ctx.grads = tuple(getattr(t, "main_grad", None)
@@ -324,7 +380,8 @@ def mlp_gelu(x: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor,
     via hipBLASLt when available for this (M, N, K); shapes the epilogue
     heuristics reject fall back to the composed path (cached, logged
     once per shape): one autograd node for bf16 (_MLPGeluFn), else
-    linear -> gelu -> linear."""
+    linear -> gelu -> linear. In that node a routed fc (gemm_route) is one
+    kernel that writes pre and h."""
     if use_hip(x):
         rows = x.numel() // x.shape[-1]
         if rows <= 4 and not torch.is_grad_enabled():

@@ -499,6 +499,83 @@ Tensor wgrad_bias(Tensor dy, Tensor x, Tensor dw, OptTensor db, bool bias_f32,
   return bout;
 }
 
+// ---- forward projection GEMM (gemm.hip) -------------------------------------
+// The shape contract of gemm_fwd, in one place: x2 [T, K] bf16 with unit
+// column stride and a row stride % 8 == 0 (>= K, < 2^22), w [N, K] bf16
+// contiguous, both bases 16 B aligned, T >= 1, N a multiple of the tile's
+// features and K of its K granule.
+const char* gemm_reject(const Tensor& x, const Tensor& w) {
+  if (!(x.is_cuda() && w.is_cuda() && x.device() == w.device()))
+    return "x and w must be on one GPU";
+  if (x.scalar_type() != torch::kBFloat16 ||
+      w.scalar_type() != torch::kBFloat16)
+    return "x and w must be bf16";
+  if (x.dim() != 2 || w.dim() != 2 || x.size(1) != w.size(1))
+    return "x must be [T, K] and w [N, K]";
+  const int64_t T = x.size(0), N = w.size(0), K = x.size(1);
+  if (T < 1 || T >= (int64_t(1) << 31)) return "T out of range";
+  if (N < DTA_GEMM_BN || N % DTA_GEMM_BN != 0 || K < DTA_GEMM_BK ||
+      K % DTA_GEMM_BK != 0 || K >= (int64_t(1) << 22) ||
+      N >= (int64_t(1) << 24))
+    return "N / K must be multiples of the tile";
+  if (((T + DTA_GEMM_BM - 1) / DTA_GEMM_BM) * (N / DTA_GEMM_BN) >=
+      (int64_t(1) << 31))
+    return "too many tiles";
+  if (!w.is_contiguous()) return "w must be contiguous";
+  if (x.stride(1) != 1) return "unit column stride";
+  const int64_t ld = T > 1 ? x.stride(0) : K;   // T == 1: never used
+  if (ld < K || ld % 8 != 0 || ld >= (int64_t(1) << 22))
+    return "the row stride of x must be >= K, % 8 == 0 and < 2^22";
+  if (reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 != 0 ||
+      reinterpret_cast<uintptr_t>(w.data_ptr()) % 16 != 0)
+    return "16-byte aligned operands";
+  return nullptr;
+}
+bool gemm_supported(Tensor x, Tensor w) { return !gemm_reject(x, w); }
+std::vector<int64_t> gemm_tile() {
+  return {DTA_GEMM_BM, DTA_GEMM_BN, DTA_GEMM_BK};
+}
+
+// y = x2 w^T (epi "none"), + bias ("bias"), or (pre, h) with h = gelu(pre)
+// ("bias_gelu"): fresh contiguous [T, N] bf16 outputs. pipe: 0 the default
+// K-loop pipeline, 1 / 2 a forced one (tools/gemm_ab.py). Capturable.
+py::object gemm_fwd(Tensor x2, Tensor w, OptTensor bias,
+                    const std::string& epi, int64_t pipe) {
+  const char* why = gemm_reject(x2, w);
+  TORCH_CHECK(!why, "gemm.fwd: ", why ? why : "");
+  const int e = epi == "none" ? GEMM_EPI_NONE
+                : epi == "bias" ? GEMM_EPI_BIAS
+                : epi == "bias_gelu" ? GEMM_EPI_BIAS_GELU : -1;
+  TORCH_CHECK(e >= 0, "gemm.fwd: epi must be none, bias or bias_gelu");
+  TORCH_CHECK(pipe >= 0 && pipe <= 2, "gemm.fwd: pipe must be 0, 1 or 2");
+  const int64_t T = x2.size(0), N = w.size(0), K = x2.size(1);
+  const bool has_b = bias.has_value() && bias->defined();
+  TORCH_CHECK(has_b == (e != GEMM_EPI_NONE),
+              "gemm.fwd: a bias goes with the bias epilogues, and only them");
+  if (has_b) {
+    check_bf16(*bias, "bias");
+    TORCH_CHECK(bias->device() == x2.device() && bias->numel() == N,
+                "bias must be bf16 [N] on x's device");
+  }
+  auto y = torch::empty({T, N}, x2.options());
+  Tensor aux = e == GEMM_EPI_BIAS_GELU ? torch::empty({T, N}, x2.options())
+                                       : Tensor();
+  GemmArgs a;
+  a.x = bfp(x2);
+  a.ld_x = T > 1 ? x2.stride(0) : K;
+  a.w = bfp(w);
+  a.bias = has_b ? bfp(*bias) : nullptr;
+  a.y = bfp_mut(y);
+  a.aux = aux.defined() ? bfp_mut(aux) : nullptr;
+  a.T = T; a.N = int(N); a.K = int(K); a.epi = e;
+  launch_gemm_nt(a, stream(), int(pipe));
+  const hipError_t err = hipGetLastError();
+  TORCH_CHECK(err == hipSuccess, "gemm launch failed: ",
+              hipGetErrorString(err));
+  if (e == GEMM_EPI_BIAS_GELU) return py::make_tuple(y, aux);
+  return py::cast(y);
+}
+
 // ---- merge plane -----------------------------------------------------------
 // What every merge entry point, fp32 or packed, requires of its tables
 // before anything is launched. offsets: an integer [n_segs + 1] table; the
@@ -1518,6 +1595,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   wg.def("supported", &wgrad_supported);
   wg.def("tile", &wgrad_tile);
   wg.def("nsplit", &wgrad_nsplit);
+  // gemm.hip: forward projections. Tests: tests/test_gemm_gpu.py.
+  py::module_ fg = m.def_submodule("gemm", "forward projection GEMM");
+  fg.def("fwd", &gemm_fwd, py::arg("x2"), py::arg("w"),
+         py::arg("bias") = py::none(), py::arg("epi") = "none",
+         py::arg("pipe") = 0);
+  fg.def("supported", &gemm_supported);
+  fg.def("tile", &gemm_tile);
   // trimmed_merge_k: its own submodule as well. CPU definition:
   // ops.trimmed_merge; tests/test_robust_merge_gpu.py holds the kernel to it
   // bit for bit.

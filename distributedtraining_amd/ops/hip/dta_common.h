@@ -55,6 +55,20 @@ DEV float fast_tanh(float x) {
   return (e - 1.0f) / (e + 1.0f);
 }
 
+// ---- GELU, tanh form (GPT-2 gelu_new) --------------------------------------
+// Shared by the elementwise map (elementwise.hip) and the GEMM epilogue
+// (gemm.hip), whose h has to equal gelu_fwd(pre) bit for bit: the one
+// multiply-add that fuses, x + (A x^2) x, is spelled out and nothing else may
+// contract (as gelu_df in elementwise.hip). It is the choice map_bf16_k's
+// vector loop was compiled with while the compiler was free to choose.
+constexpr float GELU_C = 0.7978845608028654f;   // sqrt(2/pi)
+constexpr float GELU_A = 0.044715f;
+DEV float gelu_f(float x) {
+#pragma clang fp contract(off)
+  float u = GELU_C * __builtin_fmaf((GELU_A * x) * x, x, x);
+  return (0.5f * x) * (1.0f + fast_tanh(u));
+}
+
 // ---- wave reductions (64-lane) --------------------------------------------
 DEV float wave_sum(float v) {
 #pragma unroll

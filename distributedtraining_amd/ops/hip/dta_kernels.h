@@ -436,6 +436,36 @@ struct WgradArgs {
 };
 void launch_wgrad(const WgradArgs& a, hipStream_t s);
 
+// ---- forward projection GEMM with bias / GELU epilogues (gemm.hip) ----------
+// y[T,N] = x[T,K] w[N,K]^T, bf16 operands, fp32 accumulation, one rounding per
+// output. x: row stride ld_x (elements, % 8 == 0, >= K, < 2^22), 16 B aligned
+// base; w: contiguous, 16 B aligned, as the parameters are stored; N %
+// DTA_GEMM_BN == 0, K % DTA_GEMM_BK == 0 (K < 2^22), T >= 1 arbitrary (rows
+// past T are clamped on load and never stored). y and aux are contiguous
+// [T, N], 16 B aligned; bias is bf16 [N] of any alignment.
+//   GEMM_EPI_NONE       y = bf16(acc)
+//   GEMM_EPI_BIAS       y = bf16(acc + bias[n])
+//   GEMM_EPI_BIAS_GELU  y = pre = bf16(acc + bias[n]), aux = h =
+//                       bf16(gelu_f(float(pre))): what launch_gelu_fwd gives
+//                       on the stored pre, bit for bit
+// No workspace, no atomics, no host sync; results repeat bit for bit.
+constexpr int DTA_GEMM_BM = 256;  // tokens per tile
+constexpr int DTA_GEMM_BN = 128;  // features per tile
+constexpr int DTA_GEMM_BK = 64;   // K granule of the contract
+enum GemmEpi { GEMM_EPI_NONE = 0, GEMM_EPI_BIAS = 1, GEMM_EPI_BIAS_GELU = 2 };
+// K-loop pipelines (gemm.hip header). 0 takes DTA_GEMM_PIPE_DEFAULT.
+enum GemmPipe { GEMM_PIPE_2X32 = 1, GEMM_PIPE_3X64 = 2 };
+struct GemmArgs {
+  const bf16_t* x;
+  int64_t ld_x;
+  const bf16_t *w, *bias;
+  bf16_t *y, *aux;
+  int64_t T;
+  int N, K;
+  int epi;   // GemmEpi
+};
+void launch_gemm_nt(const GemmArgs& a, hipStream_t s, int pipe = 0);
+
 // ---- embedding ------------------------------------------------------------
 // pos_p: device position offset for wpe (graph-replayable decode).
 // doc_start: optional int32 [n_tok] (packed sequences, the attention q_lo):

@@ -11,14 +11,8 @@
 
 namespace {
 
-constexpr float GELU_C = 0.7978845608028654f;   // sqrt(2/pi)
-constexpr float GELU_A = 0.044715f;
-
-DEV float gelu_f(float x) {
-  float u = GELU_C * (x + GELU_A * x * x * x);
-  return 0.5f * x * (1.0f + fast_tanh(u));
-}
-// 0.5 (1 + t) + 0.5 x sech^2(u) C (1 + 3A x^2). Which multiply-adds fuse is
+// gelu_f, GELU_C, GELU_A: dta_common.h (the GEMM epilogue shares them).
+// gelu'(x) = 0.5 (1 + t) + 0.5 x sech^2(u) C (1 + 3A x^2). Which multiply-adds fuse is
 // spelled out, not left to the compiler: left alone it contracted this
 // expression differently from one inlining context to the next (last-bit
 // differences where the two terms cancel, x << 0), and gelu_bwd_colsum_k's
