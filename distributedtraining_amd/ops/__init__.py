@@ -805,7 +805,12 @@ def causal_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
 
     GQA: k/v may have fewer heads (H_kv dividing H) — handled natively by
     the kernel (no repeat_interleave). Inputs may be permuted views of
-    [B,S,H*D] projections; only the head_dim must be contiguous.
+    [B,S,H*D] projections; only the head_dim must be contiguous. The GQA
+    backward folds the query heads of a KV head either inside one block
+    (one-pass dK/dV kernel: bf16 dk/dv stored directly, bit-repeatable; the
+    default for the shapes where it measured faster, ``DTA_ATTN_BWD_GQA=1``
+    for all) or with fp32 atomics into scratch buffers that are then cast
+    (everything else; summation order and last bits vary from run to run).
 
     ``kvlen`` (int32 [B]): right-padding mask — key j of row b is attended
     iff j < kvlen[b] (the reference's attention_mask semantics,
@@ -894,7 +899,9 @@ def qkv_attention(qkv: torch.Tensor, n_head: int,
                   k_hi: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Causal attention over a packed qkv projection [B,S,(H+2Hk)·D] →
     [B,S,H·D]. GQA when n_kv_head < n_head. kvlen/p_drop/site/q_lo/k_hi as
-    in :func:`causal_attention`."""
+    in :func:`causal_attention`. The backward stores dq/dk/dv straight into
+    one dqkv buffer; with GQA that holds for dk/dv on the one-pass route,
+    the atomic route copies them in from its fp32 buffers."""
     Hk = n_kv_head or n_head
     B, S, Fdim = qkv.shape
     D = Fdim // (n_head + 2 * Hk)

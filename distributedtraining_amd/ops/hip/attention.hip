@@ -27,6 +27,10 @@
 //     of the projection output [B,S,H*D] (and dq/dk/dv written the same
 //     way) so the model layer does zero transpose/contiguous copies.
 //   * GQA native: kv head = h / group; no repeat_interleave materialization.
+//     Backward dK/dV: attn_bwd_dkv_gqa_k walks the head group inside one
+//     block per KV head (no atomics, bf16 stores, bit-repeatable) for the
+//     shapes of dta_attn_bwd_gqa_wins; attn_bwd_dkv_k<., ATOMIC> folds the
+//     heads with fp32 atomics everywhere else.
 //   * swapped QK^T: mfma(A=K_tile, B=Q^T) puts a query's scores in lanes
 //     sharing (lane&15) so the softmax row-reduce is two shfl_xor ops;
 //     exp via the single-instruction exp2 path.
@@ -67,32 +71,47 @@ struct AttnCtx {
   uint64_t drop_s2;                 // per-head dropout seed
 };
 
+// The fields that follow the query head: a block of the GQA dK/dV kernel
+// walks every head of its group and re-derives them at each head step.
 // dout may be null (forward); its strides are then 0.
-DEV AttnCtx attn_ctx(const AttnGeom& geo, const ushort* q, const ushort* k,
-                     const ushort* v, const ushort* dout) {
+DEV void attn_ctx_set_head(AttnCtx& c, const AttnGeom& geo, const ushort* q,
+                           const ushort* dout, int h) {
+  c.h = h;
+  c.bhid = int64_t(c.b) * geo.H + h;
+  c.q = q + c.b * geo.q.batch + h * geo.q.head;
+  c.dout = dout + c.b * geo.dout.batch + h * geo.dout.head;
+  c.drop_s2 = 0;
+  if (c.thr)
+    c.drop_s2 = rng_head_seed(rng_site_seed(geo.drop.rng, geo.drop.site),
+                              uint64_t(c.bhid));
+}
+
+// Context of batch row b and query head h (kv head h / grp).
+DEV AttnCtx attn_ctx_at(const AttnGeom& geo, const ushort* q, const ushort* k,
+                        const ushort* v, const ushort* dout, int b, int h) {
   AttnCtx c;
   c.tid = threadIdx.x;
   c.lane = c.tid & 63;
   c.wid = c.tid >> 6;
   c.g = c.lane >> 4;
-  c.bhid = blockIdx.y;
-  c.b = int(c.bhid) / geo.H;
-  c.h = int(c.bhid) % geo.H;
-  c.hk = c.h / geo.grp;
-  c.q = q + c.b * geo.q.batch + c.h * geo.q.head;
+  c.b = b;
+  c.hk = h / geo.grp;
   c.k = k + c.b * geo.k.batch + c.hk * geo.k.head;
   c.v = v + c.b * geo.v.batch + c.hk * geo.v.head;
-  c.dout = dout + c.b * geo.dout.batch + c.h * geo.dout.head;
   c.sc2 = geo.scale * LOG2E;
   c.kvl = geo.kvlen ? min(geo.seq, geo.kvlen[c.b]) : geo.seq;
   c.q_lo = geo.q_lo ? geo.q_lo + int64_t(c.b) * geo.seq : nullptr;
   c.k_hi = geo.k_hi ? geo.k_hi + int64_t(c.b) * geo.seq : nullptr;
   c.thr = geo.drop.thr16;
-  c.drop_s2 = 0;
-  if (c.thr)
-    c.drop_s2 = rng_head_seed(rng_site_seed(geo.drop.rng, geo.drop.site),
-                              uint64_t(c.bhid));
+  attn_ctx_set_head(c, geo, q, dout, h);
   return c;
+}
+
+// blockIdx.y = b * H + h: one block per query head
+DEV AttnCtx attn_ctx(const AttnGeom& geo, const ushort* q, const ushort* k,
+                     const ushort* v, const ushort* dout) {
+  return attn_ctx_at(geo, q, k, v, dout, int(blockIdx.y) / geo.H,
+                     int(blockIdx.y) % geo.H);
 }
 
 // Rows past seq are loaded from the last row instead: garbage, but in
@@ -455,10 +474,83 @@ __global__ void attn_bwd_dq_k(const ushort* __restrict__ dout,
 }
 
 // ---------------- backward dK/dV ----------------
+// One 32-query tile (rows q0..q0+31 of head c.h, staged in the four LDS
+// panels) against the wave's 16 key rows: scores, probabilities from lse,
+// dS from delta, dropout, and the two accumulations. krow: the lane's key.
+template <int DTILES, bool DOC>
+DEV void dkv_tile(const AttnCtx& c, const AttnGeom& geo, const ushort* q_rm,
+                  const ushort* d_rm, const ushort* q_t, const ushort* d_t,
+                  int q0, int krow, const bf16x8* kb_, const bf16x8* vbf,
+                  const float* __restrict__ lse,
+                  const float* __restrict__ delta, f32x4* acck, f32x4* accv) {
+  const int lane = c.lane, g = c.g, seq = geo.seq, kvl = c.kvl;
+  f32x4 s0 = {0, 0, 0, 0}, s1 = {0, 0, 0, 0};
+  f32x4 dp0 = {0, 0, 0, 0}, dp1 = {0, 0, 0, 0};
+#pragma unroll
+  for (int sl = 0; sl < DTILES / 2; ++sl) {
+    const int c0 = 32 * sl + 8 * g;
+    bf16x8 qa = load_frag_rm<DTILES>(q_rm, lane & 15, c0);
+    bf16x8 qa1 = load_frag_rm<DTILES>(q_rm, 16 + (lane & 15), c0);
+    s0 = mfma_bf16(qa, kb_[sl], s0);
+    s1 = mfma_bf16(qa1, kb_[sl], s1);
+    bf16x8 doa = load_frag_rm<DTILES>(d_rm, lane & 15, c0);
+    bf16x8 doa1 = load_frag_rm<DTILES>(d_rm, 16 + (lane & 15), c0);
+    dp0 = mfma_bf16(doa, vbf[sl], dp0);
+    dp1 = mfma_bf16(doa1, vbf[sl], dp1);
+  }
+  f32x4 p0, p1, ds0, ds1;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    // roles swapped: this lane's key krow against the tile's queries
+    const int qa0 = q0 + 4 * g + r, qa1 = qa0 + 16;
+    const bool v0 = qa0 < seq &&
+        attn_visible<DOC>(qa0, krow, kvl, DOC ? doc_lo(c, qa0, seq) : 0);
+    const bool v1 = qa1 < seq &&
+        attn_visible<DOC>(qa1, krow, kvl, DOC ? doc_lo(c, qa1, seq) : 0);
+    const float l0 = lse[c.bhid * seq + (v0 ? qa0 : 0)] * LOG2E;
+    const float l1 = lse[c.bhid * seq + (v1 ? qa1 : 0)] * LOG2E;
+    p0[r] = v0 ? __builtin_exp2f(s0[r] * c.sc2 - l0) : 0.f;
+    p1[r] = v1 ? __builtin_exp2f(s1[r] * c.sc2 - l1) : 0.f;
+    const float d0 = delta[c.bhid * seq + ((qa0 < seq) ? qa0 : 0)];
+    const float d1 = delta[c.bhid * seq + ((qa1 < seq) ? qa1 : 0)];
+    if (c.thr) {
+      // element (q, k=krow): slice krow&3 of hash(q, krow>>2) — the
+      // transposed view of the SAME per-(b,h,q,k) draw the fwd/dq
+      // kernels take; dV uses the dropped P, dK the dropout-gated dS
+      const uint64_t hk0 =
+          rng_attn_hash(c.drop_s2, uint32_t(qa0), uint32_t(krow) >> 2);
+      const uint64_t hk1 =
+          rng_attn_hash(c.drop_s2, uint32_t(qa1), uint32_t(krow) >> 2);
+      const float m0 =
+          rng_keep(hk0, krow & 3, c.thr) ? geo.drop.inv_keep : 0.f;
+      const float m1 =
+          rng_keep(hk1, krow & 3, c.thr) ? geo.drop.inv_keep : 0.f;
+      // dS = A ⊙ (M/(1-p)·dp − delta); dV gets the dropped P = A·M/(1-p)
+      ds0[r] = p0[r] * (m0 * dp0[r] - d0);
+      ds1[r] = p1[r] * (m1 * dp1[r] - d1);
+      p0[r] *= m0;
+      p1[r] *= m1;
+    } else {
+      ds0[r] = p0[r] * (dp0[r] - d0);
+      ds1[r] = p1[r] * (dp1[r] - d1);
+    }
+  }
+  bf16x8 pa = scores_to_afrag(p0, p1, lane);
+  bf16x8 dsa = scores_to_afrag(ds0, ds1, lane);
+#pragma unroll
+  for (int t = 0; t < DTILES; ++t) {
+    bf16x8 dob2 = load_frag_col_lds(d_t, 8 * g, 16 * t + (lane & 15));
+    accv[t] = mfma_bf16(pa, dob2, accv[t]);
+    bf16x8 qcb = load_frag_col_lds(q_t, 8 * g, 16 * t + (lane & 15));
+    acck[t] = mfma_bf16(dsa, qcb, acck[t]);
+  }
+}
+
 // Q/dO tiles staged once per block per 32-query iteration (row-major for
 // the score mfmas, transposed for the accumulation B-fragments). With GQA
-// (grp>1) each kv head is walked once per ATTACHED q head (blockIdx.y
-// covers B*H) and results are accumulated with fp32 atomics into dk/dv.
+// (grp>1) off the one-pass route each kv head is walked once per ATTACHED
+// q head (blockIdx.y covers B*H) and results are accumulated with fp32
+// atomics into dk/dv.
 // Early waves see a few below-diagonal query tiles (probabilities masked
 // to 0) — the price of a uniform, barrier-safe loop.
 template <int DTILES, bool ATOMIC, bool DOC>
@@ -516,66 +608,8 @@ __global__ void attn_bwd_dkv_k(const ushort* __restrict__ dout,
     stage_tile<DTILES, true>(d_t, c.dout, geo.dout.seq, q0, seq, c.tid);
     __syncthreads();
     if (!live || q0 + 31 < kv0) continue;   // fully below the diagonal
-    f32x4 s0 = {0, 0, 0, 0}, s1 = {0, 0, 0, 0};
-    f32x4 dp0 = {0, 0, 0, 0}, dp1 = {0, 0, 0, 0};
-#pragma unroll
-    for (int sl = 0; sl < DTILES / 2; ++sl) {
-      const int c0 = 32 * sl + 8 * g;
-      bf16x8 qa = load_frag_rm<DTILES>(q_rm, lane & 15, c0);
-      bf16x8 qa1 = load_frag_rm<DTILES>(q_rm, 16 + (lane & 15), c0);
-      s0 = mfma_bf16(qa, kb_[sl], s0);
-      s1 = mfma_bf16(qa1, kb_[sl], s1);
-      bf16x8 doa = load_frag_rm<DTILES>(d_rm, lane & 15, c0);
-      bf16x8 doa1 = load_frag_rm<DTILES>(d_rm, 16 + (lane & 15), c0);
-      dp0 = mfma_bf16(doa, vbf[sl], dp0);
-      dp1 = mfma_bf16(doa1, vbf[sl], dp1);
-    }
-    f32x4 p0, p1, ds0, ds1;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      // roles swapped: this lane's key krow against the tile's queries
-      const int qa0 = q0 + 4 * g + r, qa1 = qa0 + 16;
-      const bool v0 = qa0 < seq &&
-          attn_visible<DOC>(qa0, krow, kvl, DOC ? doc_lo(c, qa0, seq) : 0);
-      const bool v1 = qa1 < seq &&
-          attn_visible<DOC>(qa1, krow, kvl, DOC ? doc_lo(c, qa1, seq) : 0);
-      const float l0 = lse[c.bhid * seq + (v0 ? qa0 : 0)] * LOG2E;
-      const float l1 = lse[c.bhid * seq + (v1 ? qa1 : 0)] * LOG2E;
-      p0[r] = v0 ? __builtin_exp2f(s0[r] * c.sc2 - l0) : 0.f;
-      p1[r] = v1 ? __builtin_exp2f(s1[r] * c.sc2 - l1) : 0.f;
-      const float d0 = delta[c.bhid * seq + ((qa0 < seq) ? qa0 : 0)];
-      const float d1 = delta[c.bhid * seq + ((qa1 < seq) ? qa1 : 0)];
-      if (c.thr) {
-        // element (q, k=krow): slice krow&3 of hash(q, krow>>2) — the
-        // transposed view of the SAME per-(b,h,q,k) draw the fwd/dq
-        // kernels take; dV uses the dropped P, dK the dropout-gated dS
-        const uint64_t hk0 =
-            rng_attn_hash(c.drop_s2, uint32_t(qa0), uint32_t(krow) >> 2);
-        const uint64_t hk1 =
-            rng_attn_hash(c.drop_s2, uint32_t(qa1), uint32_t(krow) >> 2);
-        const float m0 =
-            rng_keep(hk0, krow & 3, c.thr) ? geo.drop.inv_keep : 0.f;
-        const float m1 =
-            rng_keep(hk1, krow & 3, c.thr) ? geo.drop.inv_keep : 0.f;
-        // dS = A ⊙ (M/(1-p)·dp − delta); dV gets the dropped P = A·M/(1-p)
-        ds0[r] = p0[r] * (m0 * dp0[r] - d0);
-        ds1[r] = p1[r] * (m1 * dp1[r] - d1);
-        p0[r] *= m0;
-        p1[r] *= m1;
-      } else {
-        ds0[r] = p0[r] * (dp0[r] - d0);
-        ds1[r] = p1[r] * (dp1[r] - d1);
-      }
-    }
-    bf16x8 pa = scores_to_afrag(p0, p1, lane);
-    bf16x8 dsa = scores_to_afrag(ds0, ds1, lane);
-#pragma unroll
-    for (int t = 0; t < DTILES; ++t) {
-      bf16x8 dob2 = load_frag_col_lds(d_t, 8 * g, 16 * t + (lane & 15));
-      accv[t] = mfma_bf16(pa, dob2, accv[t]);
-      bf16x8 qcb = load_frag_col_lds(q_t, 8 * g, 16 * t + (lane & 15));
-      acck[t] = mfma_bf16(dsa, qcb, acck[t]);
-    }
+    dkv_tile<DTILES, DOC>(c, geo, q_rm, d_rm, q_t, d_t, q0, krow, kb_, vbf,
+                          lse, delta, acck, accv);
   }
   if (!live) return;
   // One walk for both outputs: storing dk and dv in two passes costs the
@@ -596,6 +630,195 @@ __global__ void attn_bwd_dkv_k(const ushort* __restrict__ dout,
       dvp[int64_t(row) * geo.dkv.seq + col] = f2bf(accv[t][r]);
     }
   });
+}
+
+// ---------------- backward dK/dV, GQA: the head group in one block ---------
+// grid = (ceil(S/64), B*Hk): one block owns 64 key rows of one KV head and
+// walks the grp query heads attached to it, heads ascending and inside a
+// head the 32-query tiles ascending, through dkv_tile into ONE acck/accv
+// register set. dk/dv are therefore a pure function of the inputs with a
+// fixed summation order: no fp32 buffer, no atomics, no workspace, equal
+// bits on every run. K/V fragments are loaded once per block; the head
+// fields of the context (Q/dO base, lse/delta row, dropout head seed) are
+// re-derived at every head step, the per-batch-row ones (kvl, document
+// mask) stay. Key rows that are padding or unseen keep zero accumulators.
+//
+// Staging (what differs from attn_bwd_dkv_k, which fetches every Q and dO
+// tile twice and transposes with 2 B LDS stores between two barriers):
+//   * a thread owns a ROW PAIR x 16 B chunk of Q or dO: two 16 B global
+//     loads into registers, once per tile. From those registers it writes
+//     the row-major panel (two 16 B LDS stores) and the transposed panel
+//     (eight 4 B stores: rows 2p, 2p+1 of one column are one LDS word).
+//     Lanes 0..15 of a wave hold the 16 row pairs of one chunk, so a
+//     transposed store is 4-way bank conflicted where a chunk-major lane
+//     order would be 16-way.
+//   * the loads of tile n+1 (which may belong to the next head) are issued
+//     before the MFMAs of tile n and land during them.
+//   * two LDS buffers: tile n+2 overwrites the buffer of tile n only after
+//     the barrier of tile n+1, which every wave reaches after its reads of
+//     tile n. One barrier per tile. One buffer between two barriers (same
+//     register prefetch) measured 0.4885 against 0.4824 ms at B8 H32 Hk8
+//     S512 D128 and 0.3713 against 0.3528 ms at B8 H14 Hk2 S512 D64, and
+//     was dropped (profiles/r13_gqa_dkv.md).
+// Epilogue: after the walk the LDS is free; each wave rounds its [16, D]
+// dk and dv tiles to bf16 into it once and stores them as 16 B rows.
+//
+// Budget per block (256 threads), D = 16*DTILES, one buffer =
+// 2 * 32*(D+8)*2 B row-major + 2 * D*40*2 B transposed:
+//   D   LDS (2 buffers)   acc  K/V frags  prefetch   = held across the loop
+//   32      20.0 KB        16      4         4 VGPR
+//   64      38.0 KB        32      8         4
+//  128      74.0 KB        64     16        16
+// so two blocks per CU fit at D = 128 (160 KB LDS, 512 VGPR per SIMD lane).
+template <int DTILES>
+struct GqaStage {
+  static constexpr int CPR = 2 * DTILES;       // 16 B chunks per row
+  static constexpr int PER_OP = 16 * CPR;      // (row pair, chunk) per operand
+  static constexpr int ITEMS = (2 * PER_OP + 255) / 256;   // per thread
+  static constexpr int BUF = 2 * LDS_RM_SIZE<DTILES> + 2 * LDS_T_SIZE<DTILES>;
+  s16x8 lo[ITEMS], hi[ITEMS];                  // rows 2p and 2p+1
+
+  // item i of the tile: operand (0 Q, 1 dO), row pair, first column
+  static DEV bool item(int tid, int it, int& op, int& rp, int& c8) {
+    const int i = tid + 256 * it;
+    op = i / PER_OP;
+    rp = i & 15;
+    c8 = ((i % PER_OP) >> 4) * 8;
+    return i < 2 * PER_OP;
+  }
+  // rows q0..q0+31 of head bases qh/doh, clamped like stage_tile
+  DEV void load(const ushort* qh, int64_t qs, const ushort* doh, int64_t ds,
+                int q0, int seq, int tid) {
+#pragma unroll
+    for (int it = 0; it < ITEMS; ++it) {
+      int op, rp, c8;
+      if (!item(tid, it, op, rp, c8)) continue;
+      const ushort* src = op ? doh : qh;
+      const int64_t rs = op ? ds : qs;
+      lo[it] = *reinterpret_cast<const s16x8*>(
+          src + int64_t(clamp_row(q0 + 2 * rp, seq)) * rs + c8);
+      hi[it] = *reinterpret_cast<const s16x8*>(
+          src + int64_t(clamp_row(q0 + 2 * rp + 1, seq)) * rs + c8);
+    }
+  }
+  // buf: Q row-major | dO row-major | Q transposed | dO transposed
+  DEV void store(ushort* buf, int tid) const {
+#pragma unroll
+    for (int it = 0; it < ITEMS; ++it) {
+      int op, rp, c8;
+      if (!item(tid, it, op, rp, c8)) continue;
+      ushort* rm = buf + op * LDS_RM_SIZE<DTILES> +
+                   2 * rp * LDS_RM_PITCH<DTILES> + c8;
+      *reinterpret_cast<s16x8*>(rm) = lo[it];
+      *reinterpret_cast<s16x8*>(rm + LDS_RM_PITCH<DTILES>) = hi[it];
+      ushort* t = buf + 2 * LDS_RM_SIZE<DTILES> + op * LDS_T_SIZE<DTILES> +
+                  c8 * LDS_RP + 2 * rp;
+#pragma unroll
+      for (int j = 0; j < 8; ++j)
+        *reinterpret_cast<uint32_t*>(t + j * LDS_RP) =
+            uint32_t(ushort(lo[it][j])) | uint32_t(ushort(hi[it][j])) << 16;
+    }
+  }
+};
+
+// The fp32 scale of the epilogue stays a scalar multiply: the packed
+// two-lane fp32 forms are switched off for this kernel.
+template <int DTILES, bool DOC>
+__global__ __launch_bounds__(256)
+__attribute__((target("no-packed-fp32-ops")))
+void attn_bwd_dkv_gqa_k(const ushort* __restrict__ dout,
+                        const ushort* __restrict__ q,
+                        const ushort* __restrict__ k,
+                        const ushort* __restrict__ v,
+                        const float* __restrict__ lse,
+                        const float* __restrict__ delta,
+                        ushort* __restrict__ dk, ushort* __restrict__ dv,
+                        AttnGeom geo) {
+  using Stage = GqaStage<DTILES>;
+  constexpr int PITCH = LDS_RM_PITCH<DTILES>;
+  static_assert(4 * 2 * 16 * PITCH <= 2 * Stage::BUF, "epilogue tiles fit");
+  const int n_hk = geo.H / geo.grp;
+  const int b = int(blockIdx.y) / n_hk, hk = int(blockIdx.y) % n_hk;
+  AttnCtx c = attn_ctx_at(geo, q, k, v, dout, b, hk * geo.grp);
+  const int lane = c.lane, g = c.g, seq = geo.seq, kvl = c.kvl;
+  const int kv0 = blockIdx.x * 64 + c.wid * 16;
+  const bool live = kv0 < seq;
+  const int krow = kv0 + (lane & 15);
+
+  bf16x8 kb_[DTILES / 2], vbf[DTILES / 2];
+#pragma unroll
+  for (int sl = 0; sl < DTILES / 2; ++sl) {
+    kb_[sl] = load_frag_row(c.k, geo.k.seq, clamp_row(krow, seq),
+                            32 * sl + 8 * g);
+    vbf[sl] = load_frag_row(c.v, geo.v.seq, clamp_row(krow, seq),
+                            32 * sl + 8 * g);
+  }
+  f32x4 acck[DTILES], accv[DTILES];
+#pragma unroll
+  for (int t = 0; t < DTILES; ++t) {
+    acck[t] = f32x4{0, 0, 0, 0};
+    accv[t] = f32x4{0, 0, 0, 0};
+  }
+
+  __shared__ __attribute__((aligned(16))) ushort lds[2 * Stage::BUF];
+  // the query walk of one head, as in attn_bwd_dkv_k (all block-uniform):
+  // nothing for a block of padding keys; DOC ends it at k_hi of the
+  // block's last live key
+  const int q_start =
+      (int(blockIdx.x) * 64 >= kvl) ? seq : int(blockIdx.x) * 64;
+  const int q_end =
+      DOC ? min(seq, (doc_hi(c, min(int(blockIdx.x) * 64 + 64, kvl) - 1, seq)
+                      + 31) & ~31)
+          : seq;
+  const int n_q = q_end > q_start ? (q_end - q_start + 31) / 32 : 0;
+  const int total = geo.grp * n_q;          // tiles: heads x query tiles
+
+  Stage st;
+  if (total) st.load(c.q, geo.q.seq, c.dout, geo.dout.seq, q_start, seq, c.tid);
+  int ld_h = c.h, ld_q0 = q_start;          // the tile held in st
+  int q0 = q_start;                         // the tile computed
+  for (int n = 0; n < total; ++n) {
+    ushort* buf = lds + (n & 1) * Stage::BUF;
+    st.store(buf, c.tid);
+    ld_q0 += 32;
+    if (ld_q0 >= q_end) { ld_q0 = q_start; ++ld_h; }
+    if (n + 1 < total)
+      st.load(q + b * geo.q.batch + ld_h * geo.q.head, geo.q.seq,
+              dout + b * geo.dout.batch + ld_h * geo.dout.head, geo.dout.seq,
+              ld_q0, seq, c.tid);
+    __syncthreads();
+    if (n && q0 == q_start) attn_ctx_set_head(c, geo, q, dout, c.h + 1);
+    if (live && q0 + 31 >= kv0)             // not fully below the diagonal
+      dkv_tile<DTILES, DOC>(c, geo, buf, buf + LDS_RM_SIZE<DTILES>,
+                            buf + 2 * LDS_RM_SIZE<DTILES>,
+                            buf + 2 * LDS_RM_SIZE<DTILES> + LDS_T_SIZE<DTILES>,
+                            q0, krow, kb_, vbf, lse, delta, acck, accv);
+    q0 += 32;
+    if (q0 >= q_end) q0 = q_start;
+  }
+
+  // epilogue: dk | dv tile of the wave, bf16, through LDS
+  __syncthreads();                          // every read of the walk is done
+  ushort* tile = lds + c.wid * 2 * 16 * PITCH;
+  if (live)
+    for_acc_rows<DTILES>(0, 16, lane, [&](int t, int r, int row, int col) {
+      tile[row * PITCH + col] = f2bf(acck[t][r] * geo.scale);
+      tile[(16 + row) * PITCH + col] = f2bf(accv[t][r]);
+    });
+  __syncthreads();
+  if (!live) return;
+  ushort* dkp = dk + b * geo.dkv.batch + hk * geo.dkv.head;
+  ushort* dvp = dv + b * geo.dkv.batch + hk * geo.dkv.head;
+#pragma unroll
+  for (int i = lane; i < 16 * Stage::CPR; i += 64) {
+    const int row = i / Stage::CPR, c8 = (i % Stage::CPR) * 8;
+    if (kv0 + row >= seq) continue;
+    const int64_t off = int64_t(kv0 + row) * geo.dkv.seq + c8;
+    *reinterpret_cast<s16x8*>(dkp + off) =
+        *reinterpret_cast<const s16x8*>(tile + row * PITCH + c8);
+    *reinterpret_cast<s16x8*>(dvp + off) =
+        *reinterpret_cast<const s16x8*>(tile + (16 + row) * PITCH + c8);
+  }
 }
 
 // ---------------- backward, whole head in one tile ----------------
@@ -1097,6 +1320,21 @@ void launch_attn_bwd_dkv(const bf16_t* dout, const bf16_t* q,
                               : attn_bwd_dkv_k<dt(), false, doc()>;
       kern<<<attn_grid(geo), 256, 0, s>>>(dout, q, k, v, lse, delta, dk32,
                                           dv32, dk, dv, geo);
+    });
+  });
+}
+
+void launch_attn_bwd_dkv_gqa(const bf16_t* dout, const bf16_t* q,
+                             const bf16_t* k, const bf16_t* v,
+                             const float* lse, const float* delta,
+                             bf16_t* dk, bf16_t* dv, const AttnGeom& geo,
+                             hipStream_t s) {
+  // dta_attn_bwd_gqa_shape(geo) holds; one block per (key tile, b, kv head)
+  const dim3 grid((geo.seq + 63) / 64, int64_t(geo.B) * (geo.H / geo.grp));
+  for_head_dim(geo.hd, [&](auto dt) {
+    for_doc_mask(geo, [&](auto doc) {
+      attn_bwd_dkv_gqa_k<dt(), doc()><<<grid, 256, 0, s>>>(
+          dout, q, k, v, lse, delta, dk, dv, geo);
     });
   });
 }

@@ -1424,13 +1424,44 @@ bool attn_bwd_fused_enable(bool on) {
 }
 int64_t attn_bwd_fused_calls() { return g_attn_bwd_fused_calls.load(); }
 
+// One-pass GQA dK/dV: DTA_ATTN_BWD_GQA=0|1 or attn_gqa.bwd_enable() force
+// the route off or on for every eligible shape; left alone, the measured
+// wins (dta_attn_bwd_gqa_wins) take it. Switch and counter as above;
+// bwd_enable returns whether the route was forced on, and after a
+// call the process stays forced one way or the other.
+static std::atomic<int> g_attn_bwd_gqa_force{-1};     // -1: environment
+static std::atomic<int64_t> g_attn_bwd_gqa_calls{0};
+static bool attn_bwd_gqa_forced_on() {
+  const int force = g_attn_bwd_gqa_force.load();
+  return (force < 0 ? dta_attn_bwd_gqa_env() : force) == 1;
+}
+static bool attn_bwd_gqa_on(const AttnGeom& geo) {
+  const int force = g_attn_bwd_gqa_force.load();
+  const int want = force < 0 ? dta_attn_bwd_gqa_env() : force;
+  return dta_attn_bwd_gqa_shape(geo) &&
+         (want < 0 ? dta_attn_bwd_gqa_wins(geo) : want != 0);
+}
+bool attn_bwd_gqa_enable(bool on) {
+  const bool was = attn_bwd_gqa_forced_on();
+  g_attn_bwd_gqa_force.store(on ? 1 : 0);
+  return was;
+}
+int64_t attn_bwd_gqa_calls() { return g_attn_bwd_gqa_calls.load(); }
+
+// dk/dv destination views of the direct-store kernels
+static bool dkv_views_storable(const Tensor& dk_v, const Tensor& dv_v) {
+  return dk_v.defined() && dv_v.defined() && dk_v.stride(3) == 1 &&
+         dk_v.strides() == dv_v.strides();
+}
+
 // The backward both entry points share: one fused launch for a single-tile
 // head, else delta alloc -> dQ -> dK/dV.
 // dq_v: [B,S,H,D] destination view (contiguous D), always written.
-// grp == 1: dk/dv are stored straight into the [B,S,Hk,D] views dk_v/dv_v.
-// GQA: the q heads fold into zeroed fp32 [B,Hk,S,D] buffers with atomics;
-// dk_v/dv_v are not touched and the buffers are handed back for the caller
-// to cast into place.
+// grp == 1, and GQA on the one-pass route: dk/dv are stored straight into
+// the [B,S,Hk,D] views dk_v/dv_v and nothing is handed back.
+// GQA otherwise: the q heads fold into zeroed fp32 [B,Hk,S,D] buffers with
+// atomics; dk_v/dv_v are not touched and the buffers are handed back for
+// the caller to cast into place.
 static std::pair<Tensor, Tensor> attn_bwd_into(
     const Tensor& dout, const Tensor& q, const Tensor& k, const Tensor& v,
     const Tensor& o_bshd, const Tensor& lse, double scale,
@@ -1458,6 +1489,22 @@ static std::pair<Tensor, Tensor> attn_bwd_into(
                      lse.data_ptr<float>(), delta.data_ptr<float>(),
                      bfp_mut(dq_v), geo, stream());
   Tensor dk32, dv32;
+  if (attn_bwd_gqa_on(geo)) {
+    TORCH_CHECK(dkv_views_storable(dk_v, dv_v),
+                "dk/dv views need contiguous head_dim and equal strides");
+    geo.dkv = strides_bshd(dk_v);
+    // the kernel stores 16 B row chunks
+    TORCH_CHECK(geo.dkv.batch % 8 == 0 && geo.dkv.head % 8 == 0 &&
+                    geo.dkv.seq % 8 == 0 &&
+                    reinterpret_cast<uintptr_t>(dk_v.data_ptr()) % 16 == 0 &&
+                    reinterpret_cast<uintptr_t>(dv_v.data_ptr()) % 16 == 0,
+                "dk/dv views need 16-byte aligned rows");
+    launch_attn_bwd_dkv_gqa(bfp(dout), bfp(q), bfp(k), bfp(v),
+                            lse.data_ptr<float>(), delta.data_ptr<float>(),
+                            bfp_mut(dk_v), bfp_mut(dv_v), geo, stream());
+    ++g_attn_bwd_gqa_calls;
+    return {Tensor(), Tensor()};
+  }
   if (geo.grp == 1) {
     TORCH_CHECK(dk_v.stride(3) == 1 && dk_v.strides() == dv_v.strides(),
                 "dk/dv views need contiguous head_dim and equal strides");
@@ -1477,7 +1524,8 @@ static std::pair<Tensor, Tensor> attn_bwd_into(
 }
 
 // Returns dq [B,S,H,D] and dk/dv as [B,Hk,S,D]: permuted views of
-// [B,S,Hk,D] stores, or with GQA the contiguous cast of the fp32 buffers.
+// [B,S,Hk,D] stores, or on the atomic GQA path the contiguous cast of the
+// fp32 buffers.
 std::vector<Tensor> attn_bwd(Tensor dout, Tensor q, Tensor k, Tensor v,
                              Tensor o_bshd, Tensor lse, double scale,
                              Tensor kvlen, Tensor rng, int64_t site,
@@ -1485,14 +1533,18 @@ std::vector<Tensor> attn_bwd(Tensor dout, Tensor q, Tensor k, Tensor v,
   const int64_t B = q.size(0), H = q.size(1), S = q.size(2), hd = q.size(3);
   const int64_t Hk = k.size(1);
   auto dq = torch::empty({B, S, H, hd}, q.options());
+  AttnGeom shape{};   // what the route predicate reads
+  shape.B = int(B); shape.H = int(H); shape.grp = int(H / Hk);
+  shape.seq = int(S); shape.hd = int(hd);
   Tensor dk, dv;
-  if (H == Hk) {
+  if (H == Hk || attn_bwd_gqa_on(shape)) {
     dk = torch::empty({B, S, Hk, hd}, q.options());
     dv = torch::empty_like(dk);
   }
   auto [dk32, dv32] = attn_bwd_into(dout, q, k, v, o_bshd, lse, scale, kvlen,
                                     rng, site, p, dq, dk, dv, q_lo, k_hi);
-  if (H == Hk) return {dq, dk.permute({0, 2, 1, 3}), dv.permute({0, 2, 1, 3})};
+  if (!dk32.defined())
+    return {dq, dk.permute({0, 2, 1, 3}), dv.permute({0, 2, 1, 3})};
   return {dq, dk32.to(torch::kBFloat16), dv32.to(torch::kBFloat16)};
 }
 
@@ -1588,6 +1640,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("colsum", &colsum, py::arg("x"), py::arg("dst") = py::none());
   // wgrad.hip: its own submodule (m.wgrad.bias, ...). Accuracy tests:
   // tests/test_wgrad_gpu.py, bound self-check tests/test_wgrad_cpu.py.
+  py::module_ ag = m.def_submodule("attn_gqa", "one-pass GQA dK/dV route");
+  ag.def("bwd_enable", &attn_bwd_gqa_enable);
+  ag.def("bwd_calls", &attn_bwd_gqa_calls);
+
   py::module_ wg = m.def_submodule("wgrad", "split-K weight gradient");
   wg.def("bias", &wgrad_bias, py::arg("dy"), py::arg("x"), py::arg("dw"),
          py::arg("db") = py::none(), py::arg("bias_f32") = false,

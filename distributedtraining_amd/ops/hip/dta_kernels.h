@@ -521,7 +521,8 @@ struct AttnGeom {
   float scale;
   AttnStride q, k, v, o;   // forward operands and output
   AttnStride dout, dq;     // backward: incoming and query gradient
-  AttnStride dkv;          // dk and dv of the direct-store path (grp == 1)
+  AttnStride dkv;          // dk and dv of the kernels that store them as
+                           // bf16: grp == 1, and GQA on the one-pass route
   // padding mask (reference attention_mask, right-padded batches:
   // training_manager.py:380-385): key j of batch row b is valid iff
   // j < kvlen[b]. null = no mask (all keys valid).
@@ -553,6 +554,40 @@ void launch_attn_bwd_dkv(const bf16_t* dout, const bf16_t* q,
                          const float* delta, float* dk32, float* dv32,
                          bf16_t* dk, bf16_t* dv, const AttnGeom& geo,
                          hipStream_t s);
+// GQA dK/dV in one pass: one block per (key tile, b, kv head) walks the
+// head group and stores bf16 dk/dv with the dkv strides (contiguous head
+// dim, equal strides, 16 B aligned rows). No fp32 buffers, no atomics;
+// heads then query tiles ascending, so results repeat bit for bit.
+// Needs dta_attn_bwd_gqa_shape; any seq, kvlen, dropout, document mask.
+inline bool dta_attn_bwd_gqa_shape(const AttnGeom& geo) {
+  return geo.grp >= 2 && (geo.hd == 32 || geo.hd == 64 || geo.hd == 128);
+}
+void launch_attn_bwd_dkv_gqa(const bf16_t* dout, const bf16_t* q,
+                             const bf16_t* k, const bf16_t* v,
+                             const float* lse, const float* delta,
+                             bf16_t* dk, bf16_t* dv, const AttnGeom& geo,
+                             hipStream_t s);
+// Shapes that take the one-pass kernel unless told otherwise: the measured
+// wins of profiles/r13_gqa_dkv.md only (grp 4, head dim 128, seq 64, 512
+// and 2048, 1.4 to 2.2 x), and only with at least the 512 blocks those
+// runs had: the grid is grp times smaller than the atomic kernel's, and
+// grp 7 / head dim 64 at 128 blocks lost 0.35 to 0.15 ms. Everything else
+// stays on the atomic path. DTA_ATTN_BWD_GQA=1 sends every eligible shape
+// to the one-pass kernel, =0 none.
+inline bool dta_attn_bwd_gqa_wins(const AttnGeom& geo) {
+  const int64_t blocks =
+      int64_t((geo.seq + 63) / 64) * geo.B * (geo.H / geo.grp);
+  return geo.grp == 4 && geo.hd == 128 &&
+         (geo.seq == 64 || geo.seq == 512 || geo.seq == 2048) &&
+         blocks >= 512;
+}
+inline int dta_attn_bwd_gqa_env() {   // -1 unset, else 0 / 1
+  static const int en = [] {
+    const char* e = ::getenv("DTA_ATTN_BWD_GQA");
+    return !e || !e[0] ? -1 : (e[0] == '0' ? 0 : 1);
+  }();
+  return en;
+}
 // Shapes the single-tile fused backward takes: the whole head is one
 // 64-row tile, no GQA fold, and a head dim whose panels fit LDS (128 does
 // not: 90 KB). Everything else runs dq then dkv.
