@@ -77,6 +77,12 @@ def main(argv=None) -> int:
     top.add_argument("--metrics-dir", default="metrics")
     top.add_argument("--port", type=int, default=8500,
                      help="bootstrap: HTTP port")
+    top.add_argument("--serve-weights", choices=["bf16", "int8"],
+                     default="bf16",
+                     help="serve: int8 stores the projection and head "
+                          "weights as int8 codes + group scales "
+                          "(models.quantize_for_serving); changes the "
+                          "numbers the model produces")
     top.add_argument("--src", default=None,
                      help="convert: HF checkpoint directory "
                           "(save_pretrained layout: config.json + "
@@ -151,6 +157,12 @@ def main(argv=None) -> int:
             fp = _FP(model, device=device)
             fp.load_flat_master(st["flat_master"])
             print("serving the store's current base model")
+        if ns.serve_weights == "int8":
+            from .models import quantize_for_serving
+            q = quantize_for_serving(model)
+            print(f"int8 weights: {q['converted']} layers converted, "
+                  f"{q['kept']} kept, {q['bytes_before']} -> "
+                  f"{q['bytes_after']} bytes")
         srv = InferenceServer(model, device, port=ns.port)
         srv.start()
         print(f"inference server on :{srv.port} (POST /generate)")

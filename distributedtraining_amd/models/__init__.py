@@ -4,8 +4,9 @@ from .generate import generate
 from .gpt2 import GPT2LM, CausalLMOutput
 from .llama import LlamaLM
 from .mlp import FeedforwardNN
+from .quantize import quantize_for_serving
 
-__all__ = ["build_model", "generate", "GPT2LM", "LlamaLM", "FeedforwardNN",
+__all__ = ["build_model", "generate", "quantize_for_serving", "GPT2LM", "LlamaLM", "FeedforwardNN",
            "SimpleCNN", "CausalLMOutput"]
 
 

@@ -132,7 +132,13 @@ class GPT2LM(nn.Module):
                                     for i in range(cfg.n_layer))
         self.ln_f_w = nn.Parameter(torch.ones(cfg.n_embd))
         self.ln_f_b = nn.Parameter(torch.zeros(cfg.n_embd))
+        # quantised copy of wte for the logits projection
+        # (models.quantize_for_serving); the embedding lookup stays bf16
+        self.head_q = None
         self.reset_parameters()
+
+    def _serve_head(self):
+        return self.head_q if self.head_q is not None else self.wte
 
     def reset_parameters(self) -> None:
         std = 0.02
@@ -184,7 +190,7 @@ class GPT2LM(nn.Module):
                                       p_drop=rp,
                                       site=3 * self.cfg.n_layer)
         if labels is None:
-            logits = ops.linear(x, self.wte)
+            logits = ops.linear(x, self._serve_head())
             return CausalLMOutput(loss=None, logits=logits)
         # shifted CE: predict token t+1 from position t (HF semantics);
         # head GEMM + CE fused into one pipelined node (ops.lm_head_ce)
@@ -315,7 +321,7 @@ def _gpt2_cached_forward(model: "GPT2LM", input_ids: torch.Tensor,
         x = _gpt2_block_attn_cached(blk, x, cache, i)
     cache.advance(S)
     x = ops.layer_norm(x[:, -1:], model.ln_f_w, model.ln_f_b)
-    return ops.linear(x, model.wte).squeeze(1)
+    return ops.linear(x, model._serve_head()).squeeze(1)
 
 
 def _gpt2_new_cache(self: "GPT2LM", batch: int, max_len: int, device,

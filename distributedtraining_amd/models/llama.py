@@ -114,6 +114,9 @@ class LlamaLM(nn.Module):
             self.lm_head_w = nn.Parameter(torch.empty(cfg.vocab_size, cfg.n_embd))
         cos, sin = rope_tables(cfg.n_positions, cfg.n_embd // cfg.n_head,
                                cfg.rope_theta)
+        # quantised head for the logits projection
+        # (models.quantize_for_serving); embedding and loss paths keep bf16
+        self.head_q = None
         self.register_buffer("rope_cos", cos, persistent=False)
         self.register_buffer("rope_sin", sin, persistent=False)
         self.reset_parameters()
@@ -133,7 +136,13 @@ class LlamaLM(nn.Module):
                     w.normal_(0, std / math.sqrt(2 * self.cfg.n_layer))
 
     def _head(self):
+        if self.lm_head_w is None and not self.cfg.tie_word_embeddings:
+            raise RuntimeError("the head was quantised for serving "
+                               "(quantize_for_serving): inference only")
         return self.lm_head_w if self.lm_head_w is not None else self.tok_emb
+
+    def _serve_head(self):
+        return self.head_q if self.head_q is not None else self._head()
 
     def forward(self, input_ids: torch.Tensor,
                 attention_mask: Optional[torch.Tensor] = None,
@@ -161,7 +170,8 @@ class LlamaLM(nn.Module):
             _, x = ops.add_rms_norm(x, pending, self.final_norm_w,
                                     self.cfg.norm_eps)
         if labels is None:
-            return CausalLMOutput(loss=None, logits=ops.linear(x, self._head()))
+            return CausalLMOutput(loss=None,
+                                  logits=ops.linear(x, self._serve_head()))
         tgt = labels[:, 1:]
         if attention_mask is not None:   # pad targets ignored (-100)
             tgt = tgt.masked_fill(attention_mask[:, 1:] == 0, -100)
@@ -238,7 +248,7 @@ def _llama_cached_forward(model: "LlamaLM", input_ids: torch.Tensor,
         x = _llama_block_attn_cached(blk, x, cos, sin, cache, i, pos=pos)
     cache.advance(S)
     x = ops.rms_norm(x[:, -1:], model.final_norm_w, model.cfg.norm_eps)
-    return ops.linear(x, model._head()).squeeze(1)
+    return ops.linear(x, model._serve_head()).squeeze(1)
 
 
 def _llama_new_cache(self: "LlamaLM", batch: int, max_len: int, device,

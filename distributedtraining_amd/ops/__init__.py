@@ -35,8 +35,11 @@ import torch.nn.functional as F
 
 from . import droprng
 from .backend import require_ext, use_hip
+from .w8 import (QuantWeight, dequantize_weight, linear_w8,
+                 quantize_weight_int8)
 
 __all__ = [
+    "QuantWeight", "quantize_weight_int8", "dequantize_weight",
     "layer_norm", "rms_norm", "gelu", "swiglu", "causal_attention",
     "qkv_attention", "linear", "mlp_gelu", "add_layer_norm",
     "add_rms_norm",
@@ -222,7 +225,14 @@ def linear(x: torch.Tensor, w: torch.Tensor,
     gemv wins up to ~17M-element weights (q/o 4096x4096: 12.1 vs
     22.6 us), tuned hipBLASLt wins the streaming shapes (down-proj
     22.0 vs 53.3 us at 5.3 TB/s; untuned heuristics were the original
-    1.7 TB/s problem — tuning/ carries the decode-shape selections)."""
+    1.7 TB/s problem — tuning/ carries the decode-shape selections).
+
+    ``w`` may be a ``QuantWeight`` (int8 weight-only serving, ops/w8.py;
+    inference only): up to 16 rows stream the packed weight through the
+    MFMA kernel of hip/w8_gemv.hip, more rows dequantise it for the library
+    GEMM; on the CPU the dequantised weight goes to F.linear."""
+    if isinstance(w, QuantWeight):
+        return linear_w8(x, w, b)
     if use_hip(x):
         rows = x.numel() // x.shape[-1]
         if rows <= 4 and not torch.is_grad_enabled() and _gemv_wins(rows, w):
@@ -381,7 +391,10 @@ def mlp_gelu(x: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor,
     heuristics reject fall back to the composed path (cached, logged
     once per shape): one autograd node for bf16 (_MLPGeluFn), else
     linear -> gelu -> linear. In that node a routed fc (gemm_route) is one
-    kernel that writes pre and h."""
+    kernel that writes pre and h. Quantised weights (``QuantWeight``)
+    compose linear -> gelu -> linear."""
+    if isinstance(w1, QuantWeight) or isinstance(w2, QuantWeight):
+        return linear(gelu(linear(x, w1, b1)), w2, b2)
     if use_hip(x):
         rows = x.numel() // x.shape[-1]
         if rows <= 4 and not torch.is_grad_enabled():

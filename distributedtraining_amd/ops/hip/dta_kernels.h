@@ -505,6 +505,46 @@ void launch_f32_to_bf16(const float* x, bf16_t* y, int64_t n, hipStream_t s);
 void launch_gemv(const bf16_t* x, const bf16_t* w, const bf16_t* bias,
                  bf16_t* y, int M, int64_t N, int K, hipStream_t s);
 
+// ---- int8 weight-only serving GEMM (w8_gemv.hip) ---------------------------
+// y[M,N] = x[M,K] · Wq[N,K]^T (+ bias), 1 <= M <= 16, bf16 x / bias / y,
+// Wq[n,k] = float(code) * scale[n, k / DTA_W8_GROUP]. Packed operand, rows
+// padded with zero codes to Np = ceil16(N): codes int8 [Np/16][K/64][64][16]
+// (lane order, w8_gemv.hip header), scales fp32 [Np/16][K/128][16]. K %
+// DTA_W8_GROUP == 0; x, codes, scales 16 B aligned, y and part from the
+// allocator. nsplit in [1, K / DTA_W8_GROUP] slices of K, each a multiple of
+// the group; nsplit > 1 needs part, fp32 [nsplit, M, N] (every element
+// written, no zero-fill), folded in ascending slice order. No atomics, no
+// host sync; results repeat bit for bit.
+constexpr int DTA_W8_GROUP = 128;   // K columns per scale
+constexpr int DTA_W8_ROWS = 64;     // output rows per block
+constexpr int DTA_W8_MAX_M = 16;
+// K split: two blocks per CU where K allows; a split slice is at most the
+// 1024 columns of one LDS stage, so a split block stages x once. Enough row
+// blocks alone (the LM heads) take one slice: one launch, no partials.
+inline int dta_w8_nsplit(int64_t N, int K, int cus) {
+  const int64_t rb = (N + DTA_W8_ROWS - 1) / DTA_W8_ROWS;
+  const int64_t groups = K / DTA_W8_GROUP;
+  int64_t ns = (2 * int64_t(cus) + rb - 1) / (rb > 0 ? rb : 1);
+  if (ns <= 1 || groups <= 1) return 1;
+  if (ns < (groups + 7) / 8) ns = (groups + 7) / 8;
+  if (ns > groups) ns = groups;
+  const int64_t per = (groups + ns - 1) / ns;   // no empty slice
+  return int((groups + per - 1) / per);
+}
+struct W8GemvArgs {
+  const bf16_t* x;
+  const signed char* codes;
+  const float* scales;
+  const bf16_t* bias;   // null: none
+  bf16_t* y;
+  float* part;          // nsplit > 1 only
+  int M, N, K, nsplit;
+};
+void launch_w8_gemv(const W8GemvArgs& a, hipStream_t s);
+// w [N,K] bf16 = bf16(float(code) * scale): the M > 16 route (prefill)
+void launch_w8_dequant(const signed char* codes, const float* scales,
+                       bf16_t* w, int N, int K, hipStream_t s);
+
 // ---- rope -----------------------------------------------------------------
 // pos_p: device position offset for graph-replayable decode
 void launch_rope(const bf16_t* x, const float* cos_t, const float* sin_t,
