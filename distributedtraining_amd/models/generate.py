@@ -22,9 +22,14 @@ class GraphedDecoder:
     """hipGraph-captured decode step: ~100 eager kernel launches per token
     collapse into ONE graph replay (the round-1 serving path was
     launch-bound at batch 1). Requires a graphable KVCache (device
-    position counter) — the captured i32_inc advances it every replay."""
+    position counter) — the captured i32_inc advances it every replay.
 
-    def __init__(self, model, cache, batch: int, device):
+    ``sampler(logits, tok)``, when given, is captured behind the decode step:
+    it turns the step's logits into the next step's ``self.tok`` on the device
+    (ops.sample_tokens and its rng_tick), and a token is ``replay()`` with no
+    host work at all."""
+
+    def __init__(self, model, cache, batch: int, device, sampler=None):
         assert cache.pos_dev is not None
         self.model = model
         self.cache = cache
@@ -42,6 +47,8 @@ class GraphedDecoder:
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):
             self.logits = model.decode_step(self.tok, cache)
+            if sampler is not None:
+                sampler(self.logits, self.tok)
         cache.len = len0           # capture records, does not execute
         cache.pos_dev.fill_(len0)
 
@@ -50,6 +57,11 @@ class GraphedDecoder:
         self.graph.replay()        # device pos advances inside the graph
         self.cache.len += 1
         return self.logits
+
+    def replay(self) -> None:
+        """One token of a decoder built with a sampler."""
+        self.graph.replay()
+        self.cache.len += 1
 
 
 def _sample(logits, temperature, top_k, generator, top_p=0.0):
@@ -77,14 +89,26 @@ def generate(model, input_ids: torch.Tensor, max_new_tokens: int,
              top_p: float = 0.0,
              eos_token_id: Optional[int] = None,
              generator: Optional[torch.Generator] = None,
-             use_cache: bool = False) -> torch.Tensor:
+             use_cache: bool = False,
+             seed: Optional[int] = None) -> torch.Tensor:
     """Extend ``input_ids`` [B, S] by up to ``max_new_tokens``.
 
     temperature 0 = greedy; top_k > 0 restricts sampling to the k highest
     logits; 0 < top_p < 1 restricts to the smallest nucleus of tokens
     whose probability mass exceeds top_p (applied after top_k).
     Stops early when every sequence has produced eos_token_id.
+
+    ``seed`` selects the fused sampler (ops.sample_tokens, which documents
+    where its tokens differ from the default path's): the draws come from a
+    per-generation counter that starts at ``seed``, ``generator`` is unused,
+    and on the GPU cached decode replays decode step, sampler and counter
+    tick as one graph with the host looking at ``done`` every 16 tokens.
+    Output shape and early stop are those of the default path.
     """
+    if seed is not None:
+        return _generate_seeded(model, input_ids, max_new_tokens, temperature,
+                                top_k, top_p, eos_token_id, use_cache,
+                                int(seed))
     model_was_training = model.training
     model.eval()
     n_pos = getattr(model, "cfg").n_positions
@@ -135,3 +159,79 @@ def generate(model, input_ids: torch.Tensor, max_new_tokens: int,
         if model_was_training:
             model.train()
     return ids
+
+
+_POLL = 16     # tokens between two host looks at ``done`` (seeded path)
+
+
+def _generate_seeded(model, input_ids, max_new_tokens, temperature, top_k,
+                     top_p, eos, use_cache, seed):
+    from .. import ops
+    from ..ops.backend import require_ext
+    model_was_training = model.training
+    model.eval()
+    n_pos = getattr(model, "cfg").n_positions
+    B, S = input_ids.shape
+    dev = input_ids.device
+    ctr = torch.full((1,), seed, dtype=torch.int64, device=dev)
+    done = (torch.zeros(B, dtype=torch.bool, device=dev)
+            if eos is not None else None)
+
+    def sample(logits, **kw):
+        ops.sample_tokens(logits, temperature, top_k, top_p, ctr, done=done,
+                          eos=eos, **kw)
+        if ctr.is_cuda:
+            require_ext().rng_tick(ctr)    # capturable
+        else:
+            ctr.add_(1)
+
+    try:
+        if not (use_cache and hasattr(model, "prefill")):
+            ids = input_ids
+            for _ in range(max_new_tokens):
+                tok = torch.empty(B, 1, dtype=torch.long, device=dev)
+                sample(model(input_ids=ids[:, -n_pos:]).logits[:, -1],
+                       tok=tok)
+                ids = torch.cat([ids, tok], dim=1)
+                if eos is not None and bool(done.all()):
+                    break
+            return ids
+        # the default path samples once per cache position S .. total
+        total = min(S + max_new_tokens, n_pos)
+        n_new = min(max_new_tokens, total - S + 1)
+        if n_new <= 0:
+            return input_ids
+        cache = model.new_cache(B, total, dev, graphable=input_ids.is_cuda)
+        ids = torch.zeros(B, S + n_new, dtype=torch.long, device=dev)
+        ids[:, :S] = input_ids
+        tok = torch.zeros(B, 1, dtype=torch.long, device=dev)
+
+        def sample_at_cache_pos(logits, tok):
+            sample(logits, tok=tok, ids=ids,
+                   pos=cache.pos_dev if cache.pos_dev is not None
+                   else cache.len)
+
+        sample_at_cache_pos(model.prefill(input_ids, cache), tok)
+        dec = None
+        for i in range(1, n_new):
+            if (i - 1) % _POLL == 0 and eos is not None and bool(done.all()):
+                break
+            if (dec is None and cache.pos_dev is not None
+                    and max_new_tokens >= 16):
+                dec = GraphedDecoder(model, cache, B, dev,
+                                     sampler=sample_at_cache_pos)
+                dec.tok.copy_(tok)
+            if dec is not None:
+                dec.replay()
+            else:
+                sample_at_cache_pos(model.decode_step(tok, cache), tok)
+        if eos is not None:
+            # cut where the default path stops: the first column at which
+            # every row has produced eos
+            all_done = (ids[:, S:] == eos).cummax(dim=1).values.all(dim=0)
+            if bool(all_done.any()):
+                ids = ids[:, :S + int(all_done.int().argmax()) + 1]
+        return ids
+    finally:
+        if model_was_training:
+            model.train()

@@ -35,6 +35,7 @@ import torch.nn.functional as F
 
 from . import droprng
 from .backend import require_ext, use_hip
+from .sampling import sample_cdf, sample_tokens
 from .w8 import (QuantWeight, dequantize_weight, linear_w8,
                  quantize_weight_int8)
 
@@ -53,6 +54,7 @@ __all__ = [
     "quantize_blockwise_int8", "dequantize_blockwise_int8",
     "topk_compress_blockwise",
     "dropout", "rng_tick", "wgrad_route", "gemm_route",
+    "sample_tokens", "sample_cdf",
 ]
 
 

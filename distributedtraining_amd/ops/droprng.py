@@ -28,6 +28,8 @@ import torch
 SITE_K = 0xA24BAED4963EE407
 HEAD_K = 0x9E3779B97F4A7C15
 IDX_K = 0xD1B54A32D192ED03
+# call-site salts: dropout uses 0 .. 3 * n_layer; the token sampler's is "SAMP"
+SITE_SAMPLE = 0x53414D50
 
 _U = np.uint64
 
@@ -73,6 +75,21 @@ def attn_keep_mask(bh: int, S: int, Sk: int, ctr: int, site: int,
         h = sm64(s2 + ((q << _U(24)) | (k >> _U(2))) * _U(IDX_K))
         draw = (h >> (_U(16) * (k & _U(3)))) & _U(0xFFFF)
     return draw >= t
+
+
+def sample_hash(ctr: int, rows: int) -> np.ndarray:
+    """uint64 [rows]: the token sampler's draw per row (hip/sample.hip),
+    h = sm64(s1 + row * IDX_K) under the site salt SITE_SAMPLE."""
+    with np.errstate(over="ignore"):
+        s1 = sm64(np.array(ctr, dtype=np.int64).astype(np.uint64)
+                  + _U(SITE_SAMPLE) * _U(SITE_K))
+        return sm64(s1 + np.arange(rows, dtype=np.uint64) * _U(IDX_K))
+
+
+def sample_uniform(ctr: int, rows: int) -> np.ndarray:
+    """fp64 [rows] in [0, 1): sample_hash / 2^64."""
+    return np.minimum(sample_hash(ctr, rows).astype(np.float64) / 2.0 ** 64,
+                      1.0 - 2.0 ** -53)
 
 
 # ---------------------------------------------------------------------------

@@ -1302,6 +1302,77 @@ Tensor gemv(Tensor x, Tensor w, Tensor bias) {
   return y;
 }
 
+// ---- token sampler (sample.hip) ---------------------------------------------
+// One token per row of bf16 logits [B, V] (rows may be strided, any
+// alignment), written to tok (int64 [B] or [B, 1], allocated when absent) and
+// returned. counter: the int64 [1] device counter of the draw, read only.
+// done (bool / uint8 [B]) needs eos; ids (int64 [B, total], rows may be
+// strided) needs pos, an int32 [1] device column. No host sync, no allocation
+// when tok is given: capturable.
+Tensor sample_tokens(Tensor logits, double temperature, int64_t top_k,
+                     double top_p, Tensor counter, OptTensor done,
+                     int64_t eos, OptTensor tok, OptTensor ids,
+                     OptTensor pos) {
+  TORCH_CHECK(logits.is_cuda() && logits.scalar_type() == torch::kBFloat16 &&
+                  logits.dim() == 2 && logits.size(0) >= 1,
+              "logits must be a bf16 [B, V] GPU tensor");
+  const int64_t B = logits.size(0), V = logits.size(1);
+  TORCH_CHECK(V >= 1 && V <= DTA_SAMPLE_MAX_V, "sample_tokens: 1 <= V <= ",
+              DTA_SAMPLE_MAX_V);
+  TORCH_CHECK((V == 1 || logits.stride(1) == 1) &&
+                  (B == 1 || logits.stride(0) >= V) && B < (1 << 30),
+              "logits rows must be dense, row stride >= V");
+  TORCH_CHECK(counter.numel() == 1 && counter.scalar_type() == torch::kInt64 &&
+                  counter.device() == logits.device(),
+              "counter must be an int64 [1] tensor on the logits' GPU");
+  SampleArgs a{};
+  a.logits = bfp(logits);
+  a.ld = B > 1 ? logits.stride(0) : V;
+  a.B = int(B);
+  a.V = int(V);
+  dta_sample_quantize(temperature, top_k, top_p, int(V), a);
+  a.ctr = reinterpret_cast<const unsigned long long*>(
+      counter.data_ptr<int64_t>());
+  if (done.has_value() && done->defined()) {
+    TORCH_CHECK((done->scalar_type() == torch::kBool ||
+                 done->scalar_type() == torch::kUInt8) &&
+                    done->numel() == B && done->is_contiguous() &&
+                    done->device() == logits.device(),
+                "done must be a contiguous bool / uint8 [B] tensor");
+    a.done = static_cast<unsigned char*>(done->data_ptr());
+    a.eos = eos;
+  }
+  Tensor out = (tok.has_value() && tok->defined())
+                   ? *tok
+                   : torch::empty({B}, logits.options().dtype(torch::kInt64));
+  TORCH_CHECK(out.scalar_type() == torch::kInt64 && out.numel() == B &&
+                  out.is_contiguous() && out.device() == logits.device(),
+              "tok must be a contiguous int64 [B] / [B, 1] tensor");
+  a.tok = reinterpret_cast<long long*>(out.data_ptr<int64_t>());
+  if (ids.has_value() && ids->defined()) {
+    TORCH_CHECK(pos.has_value() && pos->defined() && pos->numel() == 1 &&
+                    pos->scalar_type() == torch::kInt32 &&
+                    pos->device() == logits.device(),
+                "ids needs pos, an int32 [1] tensor on the logits' GPU");
+    TORCH_CHECK(ids->scalar_type() == torch::kInt64 && ids->dim() == 2 &&
+                    ids->size(0) == B && ids->size(1) >= 1 &&
+                    ids->size(1) < (int64_t(1) << 31) &&
+                    ids->stride(1) == 1 &&
+                    (B == 1 || ids->stride(0) >= ids->size(1)) &&
+                    ids->device() == logits.device(),
+                "ids must be an int64 [B, total] tensor with dense rows");
+    a.ids = reinterpret_cast<long long*>(ids->data_ptr<int64_t>());
+    a.ids_ld = B > 1 ? ids->stride(0) : ids->size(1);
+    a.total = int(ids->size(1));
+    a.pos_p = pos->data_ptr<int>();
+  }
+  launch_sample_tokens(a, stream());
+  const hipError_t err = hipGetLastError();
+  TORCH_CHECK(err == hipSuccess, "sample_tokens launch failed: ",
+              hipGetErrorString(err));
+  return out;
+}
+
 // ---- int8 weight-only serving GEMM (w8_gemv.hip) ----------------------------
 // The packed operand of both entry points, checked in one place: codes int8
 // [Np/16, K/64, 64, 16], scales fp32 [Np/16, K/128, 16], Np = ceil16(N).
@@ -1787,6 +1858,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("embedding_bwd", &embedding_bwd, py::arg("dy"), py::arg("ids"),
         py::arg("vocab"), py::arg("npos"),
         py::arg("doc_start") = py::none());
+  // sample.hip: the decode graph's token sampler, its own submodule, also
+  // reachable as m.sample_tokens. CPU definition: ops/sampling.py;
+  // tests/test_sample_gpu.py holds the kernel to it.
+  py::module_ smp = m.def_submodule("sample", "fused token sampler");
+  smp.def("tokens", &sample_tokens, py::arg("logits"),
+          py::arg("temperature"), py::arg("top_k"), py::arg("top_p"),
+          py::arg("counter"), py::arg("done") = py::none(),
+          py::arg("eos") = -1, py::arg("tok") = py::none(),
+          py::arg("ids") = py::none(), py::arg("pos") = py::none());
+  m.attr("sample_tokens") = smp.attr("tokens");
   m.def("kv_append", &kv_append);
   m.def("i32_inc", &i32_inc);
   m.def("gemv", &gemv);

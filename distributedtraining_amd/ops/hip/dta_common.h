@@ -147,6 +147,10 @@ DEV uint64_t sm64(uint64_t z) {
 #define DTA_RNG_SITE_K 0xA24BAED4963EE407ULL
 #define DTA_RNG_HEAD_K 0x9E3779B97F4A7C15ULL
 #define DTA_RNG_IDX_K 0xD1B54A32D192ED03ULL
+// Call-site salts: dropout uses 0 .. 3 * n_layer (models/gpt2.py); the token
+// sampler (sample.hip) hashes the row index, h = rng_elem_hash(s1, row), under
+// a salt far above them ("SAMP").
+#define DTA_RNG_SITE_SAMPLE 0x53414D50ULL
 // The chain above, spelled once: kernels call these and never name a
 // constant, a shift or the 16-bit mask themselves.
 DEV uint64_t rng_site_seed(const unsigned long long* ctr,

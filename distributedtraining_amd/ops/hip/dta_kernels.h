@@ -545,6 +545,48 @@ void launch_w8_gemv(const W8GemvArgs& a, hipStream_t s);
 void launch_w8_dequant(const signed char* codes, const float* scales,
                        bf16_t* w, int N, int K, hipStream_t s);
 
+// ---- token sampler (sample.hip) --------------------------------------------
+// One token per row of bf16 logits [B, V], row stride ld >= V elements, any
+// alignment: temperature, top-k (ties at the k-th value kept), top-p (a key is
+// kept iff the mass strictly above it is <= p * W; ties kept together) and the
+// draw h / 2^64 over the kept weights in index order, h =
+// rng_elem_hash(rng_site_seed(ctr, SITE_SAMPLE), row). scale <= 0, or a row
+// maximum that is not finite, gives the lowest index of the maximum (NaN
+// counts as -inf; an all -inf row gives 0). 1 <= V <= DTA_SAMPLE_MAX_V; rows
+// of up to 57328 logits stay in registers, wider ones are re-read from L2.
+// ctr is read only (the caller ticks it). Integer mass throughout: no float
+// atomics, results repeat bit for bit; no host sync, capturable.
+// Bookkeeping, each optional by null: done [B] bytes with eos (a done row
+// emits eos; done |= token == eos), tok [B] int64, ids [B, ids_ld] int64 with
+// the token stored at column min(*pos_p, total - 1).
+constexpr int DTA_SAMPLE_MAX_V = 1 << 20;
+struct SampleArgs {
+  const bf16_t* logits;
+  int64_t ld;
+  int B, V;
+  float scale;                    // log2(e) / temperature; <= 0: greedy
+  int top_k;                      // 0: none
+  unsigned long long top_p64;     // floor(p * 2^64); 0: none
+  const unsigned long long* ctr;
+  unsigned char* done;
+  long long eos;
+  long long* tok;
+  long long* ids;
+  int64_t ids_ld;
+  int total;
+  const int* pos_p;
+};
+// The one place the request is quantised: the scale is formed in double and
+// rounded once; top_k outside (0, V) and top_p outside (0, 1) mean no filter.
+inline void dta_sample_quantize(double temperature, int64_t top_k,
+                                double top_p, int V, SampleArgs& a) {
+  a.scale = temperature > 0.0 ? float(1.4426950408889634 / temperature) : 0.f;
+  a.top_k = (top_k > 0 && top_k < V) ? int(top_k) : 0;
+  a.top_p64 = (top_p > 0.0 && top_p < 1.0)
+                  ? (unsigned long long)(top_p * 18446744073709551616.0) : 0ull;
+}
+void launch_sample_tokens(const SampleArgs& a, hipStream_t s);
+
 // ---- rope -----------------------------------------------------------------
 // pos_p: device position offset for graph-replayable decode
 void launch_rope(const bf16_t* x, const float* cos_t, const float* sin_t,

@@ -3,7 +3,8 @@
 Deployment-side counterpart of the training roles: load a base model
 (averaged_model.pt from the store, or random init), serve
 POST /generate {"ids": [[...]], "max_new_tokens": N, "temperature": T,
-"top_k": K} -> {"ids": [[...]]}, plus GET /health. Generation runs the
+"top_k": K, "top_p": P, "seed": N} -> {"ids": [[...]]}, plus GET /health. An
+optional "seed" selects the fused on-device sampler (ops.sample_tokens). Generation runs the
 KV-cache decode path on GPU (models/generate.py); stdlib HTTP like the
 other in-framework services (utils/liveness.py, utils/bootstrap_server.py).
 """
@@ -96,12 +97,14 @@ class InferenceServer:
         top_k = int(req.get("top_k", 0))
         top_p = float(req.get("top_p", 0.0))
         eos = req.get("eos_token_id")
+        seed = req.get("seed")
         with self._lock, torch.no_grad():
             out = generate(self.model, ids, mnt, temperature=temperature,
                            top_k=top_k, top_p=top_p,
                            eos_token_id=None if eos is None else int(eos),
                            use_cache=_cached_decode(self.model,
-                                                    self.device))
+                                                    self.device),
+                           seed=None if seed is None else int(seed))
         self.served += 1
         return {"ids": out.tolist()}
 
@@ -115,9 +118,11 @@ class InferenceServer:
 
 
 def post_generate(url: str, ids, max_new_tokens: int = 32,
-                  **kw) -> Optional[list]:
+                  seed: Optional[int] = None, **kw) -> Optional[list]:
     """Client helper: POST /generate; returns completed ids or None."""
     import urllib.request
+    if seed is not None:
+        kw["seed"] = seed
     req = urllib.request.Request(
         url + "/generate",
         data=json.dumps({"ids": ids, "max_new_tokens": max_new_tokens,
