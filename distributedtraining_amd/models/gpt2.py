@@ -229,12 +229,17 @@ class KVCache:
     int32 counter (``pos_dev``) consumed by the append/embedding/decode
     kernels, so a whole decode step is hipGraph-replayable — one graph
     launch per token instead of ~100 eager launches (the round-1
-    launch-bound serving path)."""
+    launch-bound serving path).
+
+    ``split_kv``: the decode-attention route of this cache's decode steps
+    (``ops.decode_attention``: 0 one block per head, n >= 1 the split-KV
+    route with n splits, None the measured rule)."""
 
     def __init__(self, n_layer: int, batch: int, n_kv_head: int,
                  max_len: int, head_dim: int, device, dtype=None,
-                 graphable: bool = False):
+                 graphable: bool = False, split_kv: Optional[int] = None):
         dtype = dtype or torch.bfloat16
+        self.split_kv = split_kv
         self.k = [torch.zeros(batch, n_kv_head, max_len, head_dim,
                               device=device, dtype=dtype)
                   for _ in range(n_layer)]
@@ -290,7 +295,8 @@ def _gpt2_block_attn_cached(blk: GPT2Block, x: torch.Tensor,
     if S == 1:
         o = ops.decode_attention(q.reshape(B, H, D), cache.k[i],
                                  cache.v[i], cache.len + 1,
-                                 kv_len_dev=cache.pos_dev)
+                                 kv_len_dev=cache.pos_dev,
+                                 split_kv=cache.split_kv)
         o = o.view(B, 1, E)
     else:
         assert cache.len == 0, "prefill must start an empty cache"
@@ -325,12 +331,13 @@ def _gpt2_cached_forward(model: "GPT2LM", input_ids: torch.Tensor,
 
 
 def _gpt2_new_cache(self: "GPT2LM", batch: int, max_len: int, device,
-                    dtype=None, graphable: bool = False) -> KVCache:
+                    dtype=None, graphable: bool = False,
+                    split_kv: Optional[int] = None) -> KVCache:
     cfg = self.cfg
     return KVCache(cfg.n_layer, batch, cfg.n_head, max_len,
                    cfg.n_embd // cfg.n_head, device,
                    dtype or next(self.parameters()).dtype,
-                   graphable=graphable)
+                   graphable=graphable, split_kv=split_kv)
 
 
 def _gpt2_prefill(self: "GPT2LM", input_ids: torch.Tensor,

@@ -46,7 +46,7 @@ __all__ = [
     "add_rms_norm",
     "cross_entropy_loss", "lm_head_ce", "lm_head_loss",
     "embedding_fwd", "check_q_lo", "check_doc_start", "q_lo_inverse",
-    "decode_attention", "rope", "adamw_step", "delta_sub", "axpy_",
+    "decode_attention", "decode_split_plan", "rope", "adamw_step", "delta_sub", "axpy_",
     "weighted_merge", "trimmed_merge", "median_trim",
     "grad_merge_weights", "has_nan", "l2norm",
     "grad_sumsq_blocks", "grad_sumsq_partials", "step_control",
@@ -935,23 +935,64 @@ def qkv_attention(qkv: torch.Tensor, n_head: int,
     return o.transpose(1, 2).reshape(B, S, E)
 
 
+def decode_split_plan(B: int, H: int, Hk: int, Lmax: int, D: int,
+                      cus: int = 256) -> int:
+    """Split count of the split-KV decode route for a cache of capacity
+    ``Lmax`` (0: the one-block-per-head kernel). The one rule behind
+    ``decode_attention(split_kv=None)``, written from
+    profiles/r16_decode_split.md (tools/decode_attn_ab.py, MI355X): the
+    split route measured 1.7x to 44x faster at every shape of the table
+    (Llama-3-8B, GPT-2-small, Qwen2-7B heads, B 1..64, L 512..8192; the
+    arms repeat within 1 %), so it is taken wherever its contract holds.
+    The fastest count was the one nearest one block per CU with splits of
+    at least 512 keys: clamp(ceil(CUs / (B Hk)), 1, Lmax / 512), which is
+    a measured arm, within 10 % of the best arm, at every shape there.
+    Never the split route below Lmax = 512: one block per head finishes
+    there in microseconds and a second launch can only cost."""
+    grp = H // Hk if Hk > 0 and H % Hk == 0 else 0
+    if Lmax < 512 or not 1 <= grp <= 16 or D not in (64, 128):
+        return 0
+    return max(1, min(-(-cus // (B * Hk)), Lmax // 512))
+
+
+def _decode_split_candidate(B: int, Hk: int, Lmax: int, cus: int = 256) -> int:
+    """clamp(ceil(2 CUs / (B Hk)), 1, Lmax / 256), the count
+    tools/decode_attn_ab.py centres its sweep on (two resident blocks per
+    CU, splits of at least 256 keys; measured up to 25 % behind half of it)."""
+    return max(1, min(-(-2 * cus // (B * Hk)), Lmax // 256))
+
+
 def decode_attention(q: torch.Tensor, k_cache: torch.Tensor,
                      v_cache: torch.Tensor, kv_len: int,
                      scale: Optional[float] = None,
-                     kv_len_dev: Optional[torch.Tensor] = None
+                     kv_len_dev: Optional[torch.Tensor] = None,
+                     split_kv: Optional[int] = None
                      ) -> torch.Tensor:
     """Serving decode step: one new query per head attends the whole KV
     cache. q [B,H,D]; caches [B,Hk,Lmax,D] with the first kv_len rows
     valid. ``kv_len_dev`` (int32 [1] device counter holding the cache
     position BEFORE this token; effective length = *kv_len_dev + 1) makes
-    the step hipGraph-replayable. Inference-only (no autograd)."""
+    the step hipGraph-replayable. ``split_kv`` (GPU only): 0 the
+    one-block-per-head kernel, n >= 1 the split-KV MFMA route with n splits
+    of the cache (one block per KV head and split, K/V read once per KV
+    head), None asks ``decode_split_plan``. Inference-only (no autograd)."""
     if scale is None:
         scale = 1.0 / math.sqrt(q.shape[-1])
     if use_hip(q):
+        if split_kv is None:
+            split_kv = decode_split_plan(q.shape[0], q.shape[1],
+                                         k_cache.shape[1], k_cache.shape[2],
+                                         q.shape[2])
+        if split_kv < 0:
+            raise ValueError(f"decode_attention: split_kv {split_kv}")
+        len_dev = (kv_len_dev if kv_len_dev is not None
+                   else torch.empty(0, dtype=torch.int32, device=q.device))
+        if split_kv:
+            return require_ext().decode_split.attn(
+                q.contiguous(), k_cache, v_cache, kv_len, scale, len_dev,
+                split_kv)
         return require_ext().attn_decode(
-            q.contiguous(), k_cache, v_cache, kv_len, scale,
-            kv_len_dev if kv_len_dev is not None
-            else torch.empty(0, dtype=torch.int32, device=q.device))
+            q.contiguous(), k_cache, v_cache, kv_len, scale, len_dev)
     if kv_len_dev is not None:
         kv_len = int(kv_len_dev.item()) + 1
     qf = q.float().unsqueeze(2)                       # [B,H,1,D]

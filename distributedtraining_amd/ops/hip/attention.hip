@@ -31,6 +31,10 @@
 //     block per KV head (no atomics, bf16 stores, bit-repeatable) for the
 //     shapes of dta_attn_bwd_gqa_wins; attn_bwd_dkv_k<., ATOMIC> folds the
 //     heads with fp32 atomics everywhere else.
+//   * Serving decode has two routes: attn_decode_k (one block per query
+//     head, fp32 FMAs) and attn_decode_split_k + attn_decode_combine_k (one
+//     block per KV head and cache split, the head group on MFMA); see the
+//     comments at the kernels and ops.decode_split_plan.
 //   * swapped QK^T: mfma(A=K_tile, B=Q^T) puts a query's scores in lanes
 //     sharing (lane&15) so the softmax row-reduce is two shfl_xor ops;
 //     exp via the single-instruction exp2 path.
@@ -1221,6 +1225,283 @@ __global__ void attn_decode_k(const ushort* __restrict__ q,   // [B,H,D]
   }
 }
 
+// ---------------- decode, split-KV route (long-context GQA serving) --------
+// One block per (KV split, KV head, batch row): the grp <= 16 query heads of
+// a KV head are the 16 columns of one MFMA tile, so K and V leave HBM once
+// per KV head, and a long cache is cut into nsplit independent blocks whose
+// fp32 partials (m, l, acc) attn_decode_combine_k merges in index order.
+//   * The 4 waves take the split's 32-key tiles interleaved and never meet
+//     in the loop: each has a V tile of its own in LDS, ordered by
+//     wave-scope fences only (a wave's LDS operations execute in order).
+//   * Scores, swapped as in attn_fwd_k: mfma(A = K tile, B = Q^T). Q^T is
+//     D/32 B-fragments held for the whole block (column n = head hk*grp + n,
+//     zero for n >= grp). K goes from global memory straight into the
+//     A-fragments: lane (n, g) loads 16 B of key row n at column 32*step +
+//     8g, every element is used by exactly one lane.
+//   * P.V without moving P: the score tiles p0, p1 in C layout (key 4g + r
+//     and 16 + 4g + r of query n) ARE a B-fragment of the 32-deep MFMA once
+//     contraction slot 8g + j is read as key 16*(j >> 2) + 4g + (j & 3).
+//     The A-fragment (V^T: row d, same key order) is two 8 B reads of the
+//     transposed [D][DEC_VP] tile. The product is O^T: acc[t][r] is column
+//     d = 16t + 4g + r of query n, so alpha, l and 1/l are per lane, and a
+//     lane stores 4 consecutive columns.
+//   * Loads run one tile ahead in registers: K(i+1) is issued after the
+//     score MFMAs of tile i, V(i+1) after V(i) went to LDS. Rows are clamped
+//     into the split, so the look-ahead past the last tile re-reads its last
+//     row instead of branching (a branch made the compiler drain the loads).
+// Rounding points: P is rounded to bf16 before P.V, l sums the unrounded
+// fp32 p (as attn_fwd_k), partials are fp32, o is rounded once.
+constexpr int DEC_VP = 36;   // V^T tile pitch: 32 keys + 4 (18 dwords: the 4
+                             // lane groups of a staging write hit 4 bank sets)
+
+// 16 B of cache row `row` (clamped below `end`) at column c0
+DEV s16x8 dec_load(const ushort* base, int row, int end, int D, int c0) {
+  return *reinterpret_cast<const s16x8*>(
+      base + int64_t(row < end ? row : end - 1) * D + c0);
+}
+
+// K A-fragments of the 32-key tile at kv0: rows kv0 + n and kv0 + 16 + n
+template <int DTILES>
+DEV void dec_load_k(s16x8 (&ka)[DTILES / 2], s16x8 (&kb)[DTILES / 2],
+                    const ushort* kp, int kv0, int end, int lane) {
+  const int n = lane & 15, g = lane >> 4;
+#pragma unroll
+  for (int sl = 0; sl < DTILES / 2; ++sl) {
+    ka[sl] = dec_load(kp, kv0 + n, end, 16 * DTILES, 32 * sl + 8 * g);
+    kb[sl] = dec_load(kp, kv0 + 16 + n, end, 16 * DTILES, 32 * sl + 8 * g);
+  }
+}
+// V tile at kv0: vr[it] is row n + 16*(it & 1), 16 B chunk g + 4*(it >> 1)
+template <int DTILES>
+DEV void dec_load_v(s16x8 (&vr)[DTILES], const ushort* vp, int kv0, int end,
+                    int lane) {
+  const int n = lane & 15, g = lane >> 4;
+#pragma unroll
+  for (int it = 0; it < DTILES; ++it)
+    vr[it] = dec_load(vp, kv0 + n + 16 * (it & 1), end, 16 * DTILES,
+                      8 * (g + 4 * (it >> 1)));
+}
+
+template <int DTILES>  // D = 16*DTILES
+__global__ __launch_bounds__(256)
+__attribute__((target("no-packed-fp32-ops")))
+void attn_decode_split_k(const ushort* __restrict__ q,   // [B,H,D]
+                         const ushort* __restrict__ kc,  // [B,Hk,Lmax,D]
+                         const ushort* __restrict__ vc,
+                         ushort* __restrict__ o,         // [B,H,D]
+                         float* __restrict__ ws,  // [B,H,nsplit,D+4]
+                         int H, int grp, int Lmax, int kvlen,
+                         const int* __restrict__ len_p, int64_t cb, int64_t ch,
+                         int chunk, float scale) {
+  constexpr int D = 16 * DTILES;
+  constexpr int KS = DTILES / 2;            // 32-column steps of a K row
+  constexpr int VT = D * DEC_VP;            // ushorts of one wave's V^T tile
+  constexpr int COMB = 128 + 4 * 16 * D;    // floats: m[4][16] l[4][16] acc
+  constexpr int SMEM = 4 * VT * 2 > COMB * 4 ? 4 * VT * 2 : COMB * 4;
+  __shared__ __attribute__((aligned(16))) char smem[SMEM];
+
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int n = lane & 15, g = lane >> 4;
+  const int split = blockIdx.x, nsplit = gridDim.x;
+  const int hk = blockIdx.y, b = blockIdx.z;
+  if (len_p) kvlen = *len_p + 1;
+  kvlen = min(kvlen, Lmax);
+  const int start = split * chunk;
+  const int end = min(kvlen, start + chunk);
+  const int h0 = hk * grp;
+
+  if (start >= end) {   // block-uniform: nothing of this split is valid yet
+    if (tid < grp) {
+      if (nsplit == 1) {
+        for (int c = 0; c < D; ++c) o[(int64_t(b) * H + h0 + tid) * D + c] = 0;
+      } else {
+        float* row = ws + ((int64_t(b) * H + h0 + tid) * nsplit + split) *
+                              dta_decode_split_row(D);
+        *reinterpret_cast<f32x4*>(row + D) = f32x4{-INFINITY, 0.f, 0.f, 0.f};
+      }
+    }
+    return;
+  }
+
+  const ushort* kp = kc + b * cb + hk * ch;
+  const ushort* vp = vc + b * cb + hk * ch;
+  const float sc2 = scale * LOG2E;
+
+  // Q^T B-fragments: lane (n, g) holds q[head h0 + n][32*sl + 8g .. + 7]
+  bf16x8 qb[KS];
+  {
+    const ushort* qp = q + (int64_t(b) * H + h0 + min(n, grp - 1)) * D;
+#pragma unroll
+    for (int sl = 0; sl < KS; ++sl) {
+      s16x8 v = *reinterpret_cast<const s16x8*>(qp + 32 * sl + 8 * g);
+      if (n >= grp) v = s16x8{0, 0, 0, 0, 0, 0, 0, 0};
+      qb[sl] = as_bf16x8(v);
+    }
+  }
+
+  f32x4 acc[DTILES];
+#pragma unroll
+  for (int t = 0; t < DTILES; ++t) acc[t] = f32x4{0, 0, 0, 0};
+  float m_run = -INFINITY, l_run = 0.f;   // of query n, in exp2 units
+
+  ushort* vt = reinterpret_cast<ushort*>(smem) + wid * VT;
+  s16x8 ka[KS], kb[KS];   // key rows kv0 + n and kv0 + 16 + n
+  s16x8 vr[DTILES];
+  // wave wid owns tiles wid, wid + 4, ... of the split (wave-uniform loop)
+  int kv0 = start + 32 * wid;
+  dec_load_k<DTILES>(ka, kb, kp, kv0, end, lane);   // clamped: in bounds
+  // K before V here as in the loop: the wait for K at the loop top is
+  // counted against the entry that has more loads issued after K
+  __builtin_amdgcn_sched_barrier(0);
+  dec_load_v<DTILES>(vr, vp, kv0, end, lane);
+  for (; kv0 < end; kv0 += 128) {
+    f32x4 p0 = {0, 0, 0, 0}, p1 = {0, 0, 0, 0};
+#pragma unroll
+    for (int sl = 0; sl < KS; ++sl) {
+      p0 = mfma_bf16(as_bf16x8(ka[sl]), qb[sl], p0);
+      p1 = mfma_bf16(as_bf16x8(kb[sl]), qb[sl], p1);
+    }
+    // clamped: in bounds even past the last tile
+    dec_load_k<DTILES>(ka, kb, kp, kv0 + 128, end, lane);
+
+    float mx = -INFINITY;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int k0a = kv0 + 4 * g + r;
+      p0[r] = k0a < end ? p0[r] * sc2 : -INFINITY;
+      p1[r] = k0a + 16 < end ? p1[r] * sc2 : -INFINITY;
+      mx = fmaxf(mx, fmaxf(p0[r], p1[r]));
+    }
+    mx = fmaxf(mx, __shfl_xor(mx, 16));
+    mx = fmaxf(mx, __shfl_xor(mx, 32));
+    const float m_new = fmaxf(m_run, mx);   // finite: key kv0 is valid
+    const float alpha =
+        (m_run == -INFINITY) ? 0.f : __builtin_exp2f(m_run - m_new);
+    float pf[8];
+    float psum = 0.f;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      pf[r] = (p0[r] == -INFINITY) ? 0.f : __builtin_exp2f(p0[r] - m_new);
+      pf[4 + r] = (p1[r] == -INFINITY) ? 0.f : __builtin_exp2f(p1[r] - m_new);
+      psum += pf[r] + pf[4 + r];
+    }
+    psum += __shfl_xor(psum, 16);
+    psum += __shfl_xor(psum, 32);
+    l_run = l_run * alpha + psum;
+    m_run = m_new;
+    // slot 8g + j of the contraction = key 16*(j >> 2) + 4g + (j & 3)
+    const bf16x8 pb = pack_bf16x8(pf);
+
+    // V(i) registers -> transposed tile; the previous tile's reads are done
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int it = 0; it < DTILES; ++it) {
+      const int row = n + 16 * (it & 1), c8 = 8 * (g + 4 * (it >> 1));
+#pragma unroll
+      for (int j = 0; j < 8; ++j)
+        vt[(c8 + j) * DEC_VP + row] = ushort(vr[it][j]);
+    }
+    dec_load_v<DTILES>(vr, vp, kv0 + 128, end, lane);
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int t = 0; t < DTILES; ++t) {
+      const ushort* vrow = vt + (16 * t + n) * DEC_VP + 4 * g;
+      const s16x4 lo = *reinterpret_cast<const s16x4*>(vrow);
+      const s16x4 hi = *reinterpret_cast<const s16x4*>(vrow + 16);
+      const bf16x8 va =
+          as_bf16x8(__builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
+      acc[t] *= alpha;
+      acc[t] = mfma_bf16(va, pb, acc[t]);
+    }
+  }
+
+  // merge of the 4 wave partials, 16 columns wide; the V tiles are dead
+  __syncthreads();
+  float* cm = reinterpret_cast<float*>(smem);   // [4][16]
+  float* cl = cm + 64;                          // [4][16]
+  float* ca = cl + 64;                          // [4][16][D]
+  if (g == 0) {
+    cm[wid * 16 + n] = m_run;
+    cl[wid * 16 + n] = l_run;
+  }
+#pragma unroll
+  for (int t = 0; t < DTILES; ++t)
+    *reinterpret_cast<f32x4*>(ca + (wid * 16 + n) * D + 16 * t + 4 * g) =
+        acc[t];
+  __syncthreads();
+  for (int u = tid; u < 4 * D; u += 256) {   // (head, 4 columns) units
+    const int hn = u / (D / 4), d4 = (u % (D / 4)) * 4;
+    if (hn >= grp) continue;
+    float mg = -INFINITY;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) mg = fmaxf(mg, cm[w * 16 + hn]);
+    float lg = 0.f;
+    f32x4 s = {0, 0, 0, 0};
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+      const float mw = cm[w * 16 + hn];
+      const float r = (mw == -INFINITY) ? 0.f : __builtin_exp2f(mw - mg);
+      lg += cl[w * 16 + hn] * r;
+      const f32x4 a =
+          *reinterpret_cast<const f32x4*>(ca + (w * 16 + hn) * D + d4);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) s[e] = fmaf(a[e], r, s[e]);
+    }
+    const int64_t bh = int64_t(b) * H + h0 + hn;
+    if (nsplit == 1) {
+      const float inv = lg > 0.f ? 1.0f / lg : 0.f;
+      s16x4 ob;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) ob[e] = short(f2bf(s[e] * inv));
+      *reinterpret_cast<s16x4*>(o + bh * D + d4) = ob;
+    } else {
+      float* row = ws + (bh * nsplit + split) * dta_decode_split_row(D);
+      *reinterpret_cast<f32x4*>(row + d4) = s;
+      if (d4 == 0) *reinterpret_cast<f32x4*>(row + D) = f32x4{mg, lg, 0.f, 0.f};
+    }
+  }
+}
+
+// One wave per (b, h): m* over the splits, then l and acc rescaled and summed
+// in split order, o rounded once. A fixed order: the result repeats bit for
+// bit. An empty split (m = -inf) has no acc row and is skipped.
+template <int DTILES>
+__global__ __launch_bounds__(256)
+__attribute__((target("no-packed-fp32-ops")))
+void attn_decode_combine_k(const float* __restrict__ ws,
+                           ushort* __restrict__ o, int BH, int nsplit) {
+  constexpr int D = 16 * DTILES;
+  constexpr int CPL = D / 64;
+  const int lane = threadIdx.x & 63;
+  const int bh = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (bh >= BH) return;
+  const int64_t rs = dta_decode_split_row(D);
+  const float* base = ws + int64_t(bh) * nsplit * rs;
+  float mg = -INFINITY;
+  for (int s = 0; s < nsplit; ++s) mg = fmaxf(mg, base[s * rs + D]);
+  float lg = 0.f;
+  float acc[CPL];
+#pragma unroll
+  for (int c = 0; c < CPL; ++c) acc[c] = 0.f;
+  for (int s = 0; s < nsplit; ++s) {
+    const float* row = base + s * rs;
+    const float ms = row[D];
+    if (ms == -INFINITY) continue;   // wave-uniform
+    const float r = __builtin_exp2f(ms - mg);
+    lg += row[D + 1] * r;
+#pragma unroll
+    for (int c = 0; c < CPL; ++c)
+      acc[c] = fmaf(row[64 * c + lane], r, acc[c]);
+  }
+  const float inv = lg > 0.f ? 1.0f / lg : 0.f;
+#pragma unroll
+  for (int c = 0; c < CPL; ++c)
+    o[int64_t(bh) * D + 64 * c + lane] = f2bf(acc[c] * inv);
+}
+
 // ---------------- mfma layout probes ----------------
 __global__ void mfma_probe16_k(const ushort* A, const ushort* B, float* D) {
   const int lane = threadIdx.x & 63;
@@ -1372,5 +1653,21 @@ void launch_attn_decode(const bf16_t* q, const bf16_t* kc, const bf16_t* vc,
   for_head_dim<false>(hd, [&](auto dt) {
     attn_decode_k<dt()><<<B * H, 256, 0, s>>>(q, kc, vc, o, B, H, grp, kvlen,
                                               len_p, cb, ch, scale);
+  });
+}
+
+void launch_attn_decode_split(const bf16_t* q, const bf16_t* kc,
+                              const bf16_t* vc, bf16_t* o, float* ws, int B,
+                              int H, int grp, int Lmax, int kvlen,
+                              const int* len_p, int hd, int64_t cb, int64_t ch,
+                              float scale, int nsplit, hipStream_t s) {
+  const dim3 grid(nsplit, H / grp, B);
+  const int chunk = dta_decode_split_chunk(Lmax, nsplit);
+  for_head_dim<false>(hd, [&](auto dt) {
+    attn_decode_split_k<dt()><<<grid, 256, 0, s>>>(
+        q, kc, vc, o, ws, H, grp, Lmax, kvlen, len_p, cb, ch, chunk, scale);
+    if (nsplit > 1)
+      attn_decode_combine_k<dt()><<<(B * H + 3) / 4, 256, 0, s>>>(ws, o, B * H,
+                                                                  nsplit);
   });
 }

@@ -1747,6 +1747,46 @@ Tensor attn_decode(Tensor q, Tensor kc, Tensor vc, int64_t kv_len,
   return o;
 }
 
+// Split-KV decode attention (attn_decode_split_k + attn_decode_combine_k):
+// same operands as attn_decode, nsplit blocks per (batch row, KV head). The
+// fp32 partials live in an allocator workspace on the current stream, so the
+// call captures and replays.
+Tensor attn_decode_split(Tensor q, Tensor kc, Tensor vc, int64_t kv_len,
+                         double scale, Tensor len_dev, int64_t nsplit) {
+  check_bf16(q, "q"); check_bf16(kc, "kcache"); check_bf16(vc, "vcache");
+  TORCH_CHECK(q.dim() == 3 && kc.dim() == 4, "q [B,H,D], cache [B,Hk,L,D]");
+  const int B = int(q.size(0)), H = int(q.size(1)), hd = int(q.size(2));
+  const int Hk = int(kc.size(1));
+  TORCH_CHECK(hd == 64 || hd == 128, "decode head dim must be 64/128");
+  TORCH_CHECK(H % Hk == 0 && kv_len <= kc.size(2), "bad cache geometry");
+  TORCH_CHECK(q.is_contiguous() && kc.is_contiguous() && vc.is_contiguous() &&
+                  kc.size(0) == B && kc.size(3) == hd &&
+                  vc.sizes() == kc.sizes(),
+              "split decode needs contiguous q and [B,Hk,L,D] caches");
+  const int grp = H / Hk;
+  TORCH_CHECK(1 <= grp && grp <= 16, "split decode: 1 <= H / Hk <= 16");
+  TORCH_CHECK(nsplit >= 1 && nsplit <= 1024, "split decode: 1 <= nsplit <= 1024");
+  TORCH_CHECK(B <= 65535 && Hk <= 65535 && kc.size(2) < (int64_t(1) << 30),
+              "split decode: grid limits");
+  const int* lp = nullptr;
+  if (len_dev.numel()) {
+    TORCH_CHECK(len_dev.scalar_type() == torch::kInt32 && len_dev.is_cuda(),
+                "len_dev must be an int32 GPU scalar");
+    lp = len_dev.data_ptr<int>();
+  }
+  auto o = torch::empty_like(q);
+  Tensor ws;
+  if (nsplit > 1)
+    ws = torch::empty({B, H, nsplit, dta_decode_split_row(hd)},
+                      q.options().dtype(torch::kFloat32));
+  launch_attn_decode_split(bfp(q), bfp(kc), bfp(vc), bfp_mut(o),
+                           nsplit > 1 ? ws.data_ptr<float>() : nullptr, B, H,
+                           grp, int(kc.size(2)), int(kv_len), lp, hd,
+                           kc.stride(0), kc.stride(1), float(scale),
+                           int(nsplit), stream());
+  return o;
+}
+
 // ---- mfma self-test --------------------------------------------------------
 Tensor mfma_selftest_16(Tensor A, Tensor B) {
   check_bf16(A, "A"); check_bf16(B, "B");
@@ -1888,6 +1928,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_bwd_fused_enable", &attn_bwd_fused_enable);
   m.def("attn_bwd_fused_calls", &attn_bwd_fused_calls);
   m.def("attn_decode", &attn_decode);
+  // split-KV decode route: its own submodule (m.decode_split.attn).
+  // Accuracy tests: tests/test_decode_split_gpu.py.
+  py::module_ ds = m.def_submodule("decode_split", "split-KV decode attention");
+  ds.def("attn", &attn_decode_split);
   m.def("mfma_selftest_16", &mfma_selftest_16);
   m.def("mfma_selftest_32", &mfma_selftest_32);
 }

@@ -698,6 +698,23 @@ void launch_attn_decode(const bf16_t* q, const bf16_t* kc, const bf16_t* vc,
                         const int* len_p, int hd, int64_t cb, int64_t ch,
                         float scale, hipStream_t s);
 
+// Split-KV route: one block per (KV split, batch row, KV head), the head
+// group (1 <= grp <= 16) on MFMA. Split s owns the keys
+// [s * chunk, min(kvlen, (s + 1) * chunk)); the chunk comes from the cache
+// capacity Lmax, so the launch geometry never depends on *len_p.
+inline int dta_decode_split_chunk(int Lmax, int nsplit) {
+  return 32 * ((Lmax + 32 * nsplit - 1) / (32 * nsplit));
+}
+// fp32 partial of one (b, h, split): acc[hd], then m, l (exp2 units), 2 pad
+constexpr int64_t dta_decode_split_row(int hd) { return hd + 4; }
+// ws: [B, H, nsplit, dta_decode_split_row(hd)] fp32, unused (may be null)
+// when nsplit == 1: the block then normalises and stores o itself.
+void launch_attn_decode_split(const bf16_t* q, const bf16_t* kc,
+                              const bf16_t* vc, bf16_t* o, float* ws, int B,
+                              int H, int grp, int Lmax, int kvlen,
+                              const int* len_p, int hd, int64_t cb, int64_t ch,
+                              float scale, int nsplit, hipStream_t s);
+
 // ---- mfma layout self-test ------------------------------------------------
 // D[32,32] = A[32,16] x B[16,32] and D[16,16] = A[16,32] x B[32,16]
 void launch_mfma_probe_32(const bf16_t* A, const bf16_t* B, float* D,
