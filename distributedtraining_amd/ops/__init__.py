@@ -1599,16 +1599,38 @@ def delta_sub(w: torch.Tensor, base: torch.Tensor,
     return out
 
 
-def _packed(x) -> bool:
-    """A parallel.comm.PackedDeltas (named by shape: comm imports ops)."""
-    return not isinstance(x, torch.Tensor) and hasattr(x, "kind")
+def _delta_store(deltas):
+    """``(data, scales, block)`` of N gathered deltas, as the extension's
+    entry points take them, for a plain fp32 [N, P] tensor or a
+    parallel.comm.PackedDeltas of any kind (told by shape: comm imports ops).
+    Kind "fp32" is its tensor. ``scales`` is None for a plain tensor, which
+    goes to the fp32 entries; the packed entries get an empty one where the
+    form has none."""
+    if isinstance(deltas, torch.Tensor):
+        return deltas, None, 0
+    if deltas.kind == "fp32":
+        return deltas.data, None, 0
+    scales = deltas.scales if deltas.scales is not None else \
+        torch.empty(0, dtype=torch.float32, device=deltas.data.device)
+    return deltas.data, scales, deltas.block
 
 
-def _packed_args(pd):
-    """(data, scales, block) as the packed bindings take them."""
-    scales = (pd.scales if pd.scales is not None
-              else torch.empty(0, dtype=torch.float32, device=pd.data.device))
-    return pd.data, scales, pd.block
+def _delta_rows(deltas, sliced=False):
+    """What the CPU definitions read: ``row(i)`` -> fp32 [P], or with
+    ``sliced`` ``rows(lo, hi)`` -> fp32 [N, hi - lo]. A tensor and the dense
+    kinds are indexed as they lie; int8 and topk are dequantised a row at a
+    time, or whole before the first slice."""
+    if isinstance(deltas, torch.Tensor):
+        dense = deltas
+    elif deltas.data.dtype in (torch.float32, torch.bfloat16):
+        dense = deltas.data
+    elif sliced:
+        dense = deltas.dequantize()
+    else:
+        return deltas.row
+    if sliced:
+        return lambda lo, hi: dense[:, lo:hi].float()
+    return lambda i: dense[i].float()
 
 
 def quantize_blockwise_int8(flat: torch.Tensor, block: int = 4096,
@@ -1618,21 +1640,17 @@ def quantize_blockwise_int8(flat: torch.Tensor, block: int = 4096,
     (the CPU path); the GPU kernel equals it bit for bit, reads both planes
     once and never writes the fp32 difference."""
     if use_hip(flat):
-        def plane(t):
-            # the kernel reads 16 B vectors: a row of an odd-width stack
-            # is copied to an allocation of its own
-            t = t.contiguous()
-            return t if t.data_ptr() % 16 == 0 else t.clone()
         q, scale = require_ext().quantize_int8(
-            plane(flat), flat.new_empty(0) if base is None else plane(base),
-            block)
+            _plane16(flat),
+            flat.new_empty(0) if base is None else _plane16(base), block)
         return q, scale
     from ..parallel.comm import quantize_blockwise_int8 as _q
     return _q(flat if base is None else flat.float() - base.float(), block)
 
 
 def _plane16(t: torch.Tensor) -> torch.Tensor:
-    """Contiguous and 16 B aligned, as the kernels' vector loads need."""
+    """Contiguous and 16 B aligned, as the kernels' vector loads need: a
+    row of an odd-width stack is copied to an allocation of its own."""
     t = t.contiguous()
     return t if t.data_ptr() % 16 == 0 else t.clone()
 
@@ -1707,10 +1725,11 @@ def axpy_(w: torch.Tensor, x, alpha: float = 1.0) -> torch.Tensor:
     may stay ``-0.0``."""
     if isinstance(x, tuple):
         pd, i = x
-        if pd.kind == "fp32":
-            return axpy_(w, pd.data[i], alpha)
+        data, scales, block = _delta_store(pd)
+        if scales is None:
+            return axpy_(w, data[i], alpha)
         if use_hip(w):
-            require_ext().axpy_packed(w, *_packed_args(pd), i, alpha)
+            require_ext().axpy_packed(w, data, scales, block, i, alpha)
             return w
         return w.add_(pd.row(i).to(w.dtype), alpha=alpha)
     if use_hip(w):
@@ -1731,23 +1750,23 @@ def weighted_merge(base: torch.Tensor, deltas,
     compressed in memory; the result equals this call on
     ``deltas.dequantize()``).
     """
-    if _packed(deltas) and deltas.kind == "fp32":
-        deltas = deltas.data
     N, P = deltas.shape
     if out is None:
         out = torch.empty_like(base)
     if use_hip(base):
-        if _packed(deltas):
+        data, scales, block = _delta_store(deltas)
+        if scales is None:
+            require_ext().weighted_merge(base, data, W,
+                                         offsets.to(base.device), out)
+        else:
             require_ext().weighted_merge_packed(
-                base, *_packed_args(deltas), W, offsets.to(base.device), out)
-            return out
-        require_ext().weighted_merge(base, deltas, W, offsets.to(base.device), out)
+                base, data, scales, block, W, offsets.to(base.device), out)
         return out
     seg = _seg_ids(offsets, P)
     acc = torch.zeros(P, dtype=torch.float32)
+    row = _delta_rows(deltas)
     for i in range(N):
-        di = deltas.row(i) if _packed(deltas) else deltas[i].float()
-        acc += W[i].float()[seg] * (base.float() + di)
+        acc += W[i].float()[seg] * (base.float() + row(i))
     out.copy_(acc.to(out.dtype))
     return out
 
@@ -1832,17 +1851,14 @@ def trimmed_merge(base: torch.Tensor, deltas, trim: int,
     overwritten. Both results live on ``base``'s device; the op does not
     sync. The CPU path is the definition, the GPU kernel equals it bit for
     bit (hip/merge.hip, trimmed_merge_k)."""
-    if _packed(deltas):
-        if deltas.kind == "topk":
-            raise ValueError(
-                "trimmed_merge: top-k deltas are refused. Most coordinates "
-                "are sent by fewer than half of the miners, so a "
-                "coordinate-wise median would zero almost every element; "
-                "exchange fp32, bf16 or int8 deltas for the robust merge")
-        if deltas.kind == "fp32":
-            deltas = deltas.data
-    if not _packed(deltas) and (deltas.dim() != 2
-                                or deltas.dtype != torch.float32):
+    if getattr(deltas, "kind", None) == "topk":
+        raise ValueError(
+            "trimmed_merge: top-k deltas are refused. Most coordinates "
+            "are sent by fewer than half of the miners, so a "
+            "coordinate-wise median would zero almost every element; "
+            "exchange fp32, bf16 or int8 deltas for the robust merge")
+    if isinstance(deltas, torch.Tensor) and (deltas.dim() != 2
+                                             or deltas.dtype != torch.float32):
         raise ValueError("trimmed_merge: deltas must be an fp32 [N, P] "
                          "tensor or a PackedDeltas")
     N, P = deltas.shape
@@ -1866,26 +1882,13 @@ def trimmed_merge(base: torch.Tensor, deltas, trim: int,
     else:
         outside.zero_()
     if use_hip(base):
-        if _packed(deltas):
-            data, scales, block = _packed_args(deltas)
-        else:
-            data, scales, block = deltas, base.new_empty(0), 0
-        require_ext().robust.trimmed_merge(base, data, scales, block, trim,
-                                           out, outside)
+        data, scales, block = _delta_store(deltas)
+        require_ext().robust.trimmed_merge(
+            base, data, base.new_empty(0) if scales is None else scales,
+            block, trim, out, outside)
         return out, outside
-    if _packed(deltas):
-        if deltas.kind == "bf16":
-            def rows(lo, hi):
-                return deltas.data[:, lo:hi].to(torch.float32)
-        else:
-            full = deltas.dequantize()
-
-            def rows(lo, hi):
-                return full[:, lo:hi]
-    else:
-        def rows(lo, hi):
-            return deltas[:, lo:hi]
-    _trimmed_merge_cpu(base, rows, trim, out, outside)
+    _trimmed_merge_cpu(base, _delta_rows(deltas, sliced=True), trim, out,
+                       outside)
     return out, outside
 
 
@@ -1896,23 +1899,22 @@ def grad_merge_weights(g: torch.Tensor, base: torch.Tensor,
 
     The averager's manual meta-gradient (averaging_logic.py:512-522).
     ``deltas``: [N, P] fp32 or a PackedDeltas, as in weighted_merge."""
-    if _packed(deltas) and deltas.kind == "fp32":
-        deltas = deltas.data
     N, P = deltas.shape
     S = offsets.numel() - 1
     if use_hip(g):
-        if _packed(deltas):
-            return require_ext().grad_merge_weights_packed(
-                g, base, *_packed_args(deltas), merged, offsets.to(g.device))
-        return require_ext().grad_merge_weights(g, base, deltas, merged,
-                                                offsets.to(g.device))
+        data, scales, block = _delta_store(deltas)
+        if scales is None:
+            return require_ext().grad_merge_weights(g, base, data, merged,
+                                                    offsets.to(g.device))
+        return require_ext().grad_merge_weights_packed(
+            g, base, data, scales, block, merged, offsets.to(g.device))
     seg = _seg_ids(offsets, P)
     gw = torch.zeros(N, S, dtype=torch.float32)
     diff_base = base.float() - merged.float()
     gf = g.float()
+    row = _delta_rows(deltas)
     for i in range(N):
-        di = deltas.row(i) if _packed(deltas) else deltas[i].float()
-        contrib = gf * (diff_base + di)
+        contrib = gf * (diff_base + row(i))
         gw[i] = torch.zeros(S).index_add_(0, seg, contrib)
     return gw
 

@@ -577,9 +577,9 @@ py::object gemm_fwd(Tensor x2, Tensor w, OptTensor bias,
 }
 
 // ---- merge plane -----------------------------------------------------------
-// What every merge entry point, fp32 or packed, requires of its tables
-// before anything is launched. offsets: an integer [n_segs + 1] table; the
-// kernels read int64, so an int32 table is converted, never reinterpreted.
+// What every merge entry point requires of its tables before anything is
+// launched. offsets: an integer [n_segs + 1] table; the kernels read int64,
+// so an int32 table is converted, never reinterpreted.
 int merge_n_models(int64_t n) {
   TORCH_CHECK(n >= 1 && n <= DTA_MERGE_MAX_MODELS,
               "merge: 1 <= n_models <= ", DTA_MERGE_MAX_MODELS);
@@ -598,41 +598,160 @@ int merge_n_segs(const Tensor& offsets) {
 Tensor merge_offsets(const Tensor& offsets, const Tensor& base) {
   return offsets.to(base.device(), torch::kInt64).contiguous();
 }
-// W [n_models, n_segs] as fp32 on base's device; it and the offsets must fit
-// the dynamic LDS weighted_merge_k caches them in
-Tensor merge_weights(const Tensor& W, const Tensor& base, int n_models,
-                     int n_segs) {
-  TORCH_CHECK(W.dim() == 2 && W.size(0) == n_models && W.size(1) == n_segs,
-              "W must be [n_models, n_segs]");
-  TORCH_CHECK(dta_merge_shmem(n_models, n_segs) <= DTA_MERGE_LDS_LIMIT,
-              "offsets + W ([", n_models, ", ", n_segs,
-              "]) do not fit the LDS budget of ", DTA_MERGE_LDS_LIMIT, " B");
-  return W.to(base.device(), torch::kFloat32).contiguous();
+
+bool aligned16(const Tensor& t) {
+  return reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0;
 }
-// an fp32 plane of P elements. The fp32 kernels read one element per lane,
-// so unlike the packed ones (check_plane) they ask for no 16-byte alignment
-void check_plane_f32(const Tensor& t, int64_t P, const char* name) {
+// an fp32 plane of P elements. The fp32 merge kernels read one element per
+// lane, so their entries ask for no alignment; every other reads 16 B vectors
+void check_plane(const Tensor& t, int64_t P, const char* name,
+                 bool aligned = true) {
   check_f32(t, name);
   TORCH_CHECK(t.numel() == P, name, " must have P elements");
+  if (aligned) TORCH_CHECK(aligned16(t), name, " must be 16-byte aligned");
 }
-int check_deltas_f32(const Tensor& deltas, int64_t P) {
-  check_f32(deltas, "deltas");
-  TORCH_CHECK(P >= 1 && deltas.dim() == 2 && deltas.size(1) == P,
-              "deltas must be [N, P]");
-  return merge_n_models(deltas.size(0));
+void check_quant_block(int64_t block) {
+  TORCH_CHECK(block >= DTA_QUANT_MIN_BLOCK && block <= DTA_QUANT_MAX_BLOCK &&
+                  (block & (block - 1)) == 0,
+              "block must be a power of two in [", DTA_QUANT_MIN_BLOCK, ", ",
+              DTA_QUANT_MAX_BLOCK, "]");
+}
+int block_shift(int64_t block) {
+  int shift = 0;
+  while ((int64_t(1) << shift) < block) ++shift;
+  return shift;
+}
+// the top-k format's limits (comm.check_topk_format); returns nb
+int64_t check_topk_format(int64_t P, int64_t k, int64_t block) {
+  TORCH_CHECK(P >= 1, "topk deltas: empty plane");
+  TORCH_CHECK(block >= DTA_TOPK_MIN_BLOCK && block <= DTA_TOPK_MAX_BLOCK &&
+                  (block & (block - 1)) == 0,
+              "topk block must be a power of two in [", DTA_TOPK_MIN_BLOCK,
+              ", ", DTA_TOPK_MAX_BLOCK, "]");
+  TORCH_CHECK(k >= 4 && k % 4 == 0 && k <= block / 4,
+              "topk k must be a multiple of 4 in [4, block / 4]");
+  const int64_t nb = (P + block - 1) / block;
+  TORCH_CHECK(nb < (int64_t(1) << 31), "too many top-k blocks");
+  return nb;
 }
 
-void weighted_merge(Tensor base, Tensor deltas, Tensor W, Tensor offsets,
-                    Tensor out) {
+// ---- the wire form of gathered deltas ----------------------------------------
+// The dtype of `data` says which of the four forms N rows of deltas are in
+// (dta_kernels.h, DeltaStore); this is the one place that reads it. -1: none.
+int delta_kind(const Tensor& data) {
+  switch (data.scalar_type()) {
+    case torch::kFloat32: return DELTA_F32;
+    case torch::kBFloat16: return DELTA_BF16;
+    case torch::kInt8: return DELTA_I8;
+    case torch::kInt32: return DELTA_TOPK;
+    default: return -1;
+  }
+}
+// The forms an entry point takes, a bit per DeltaKind. The top-k form has no
+// export names of its own: the packed entries take int32 entries as they
+// take bf16 or int8 data, and quantize_int8 makes them when topk_k > 0.
+constexpr int TAKES_F32 = 1 << DELTA_F32;
+constexpr int TAKES_PACKED = (1 << DELTA_BF16) | (1 << DELTA_I8);
+constexpr int TAKES_TOPK = 1 << DELTA_TOPK;
+
+// (data, scales, block) of N rows of a P-element plane, checked, as the store
+// the launchers take:
+//   fp32  data [N, P]; scales and block unused.
+//   bf16  data [N, P]; scales and block unused.
+//   int8  data [N, nb*block] codes, scales [N, nb] fp32.
+//   topk  data int32 [N, nb*k] entries; k is data.size(1) / nb.
+// Data of a form the entry does not take is held to the entry's own form and
+// refused by that form's dtype check.
+DeltaStore delta_store(const Tensor& data, const Tensor& scales,
+                       int64_t block, int64_t P, int takes) {
+  const int kind = delta_kind(data);
+  const bool taken = kind >= 0 && ((takes >> kind) & 1);
+  DeltaStore d{};
+  if (takes == TAKES_F32 || (taken && kind == DELTA_F32)) {
+    check_f32(data, "deltas");
+    TORCH_CHECK(P >= 1 && data.dim() == 2 && data.size(1) == P,
+                "deltas must be [N, P]");
+    merge_n_models(data.size(0));
+    d.kind = DELTA_F32;
+    d.packed = PackedView{data.data_ptr(), nullptr, P, 0, 0, DELTA_F32};
+    return d;
+  }
+  if (taken && kind == DELTA_TOPK) {
+    TORCH_CHECK(data.dim() == 2 && P >= 1 && block >= 1,
+                "topk entries must be [N, nb*k]");
+    const int64_t k = data.size(1) / ((P + block - 1) / block);
+    const int64_t nb = check_topk_format(P, k, block);
+    TORCH_CHECK(data.is_cuda() && data.is_contiguous(),
+                "topk entries must be a contiguous int32 [N, nb*k] GPU "
+                "tensor");
+    TORCH_CHECK(data.size(0) >= 1 && data.size(0) <= DTA_MERGE_MAX_MODELS,
+                "topk deltas: 1 <= n_models <= ", DTA_MERGE_MAX_MODELS);
+    TORCH_CHECK(data.size(1) == nb * k,
+                "topk entries must be [N, nb*k], nb = ceil(P / block)");
+    TORCH_CHECK(aligned16(data), "topk entries must be 16-byte aligned");
+    d.kind = DELTA_TOPK;
+    d.topk = TopkView{data.data_ptr<int>(), nb * k, block_shift(block),
+                      int(k)};
+    return d;
+  }
+  TORCH_CHECK(data.is_cuda() && data.dim() == 2 && data.is_contiguous(),
+              "packed data must be a contiguous [N, cols] GPU tensor");
+  TORCH_CHECK(data.size(0) >= 1 && data.size(0) <= DTA_MERGE_MAX_MODELS,
+              "packed deltas: 1 <= n_models <= ", DTA_MERGE_MAX_MODELS);
+  TORCH_CHECK(aligned16(data), "packed data must be 16-byte aligned");
+  TORCH_CHECK(P >= 1, "packed deltas: empty plane");
+  if (kind == DELTA_BF16) {
+    TORCH_CHECK(data.size(1) == P, "bf16 deltas must be [N, P]");
+    d.kind = DELTA_BF16;
+    d.packed = PackedView{data.data_ptr(), nullptr, P, 0, 0, DELTA_BF16};
+    return d;
+  }
+  TORCH_CHECK(kind == DELTA_I8, "packed data must be bf16 or int8");
+  check_quant_block(block);
+  const int64_t nb = (P + block - 1) / block;
+  TORCH_CHECK(data.size(1) == nb * block,
+              "int8 codes must be [N, nb*block], nb = ceil(P / block)");
+  check_f32(scales, "scales");
+  TORCH_CHECK(scales.dim() == 2 && scales.size(0) == data.size(0) &&
+                  scales.size(1) == nb, "scales must be [N, nb]");
+  d.kind = DELTA_I8;
+  d.packed = PackedView{data.data_ptr(), scales.data_ptr<float>(), nb * block,
+                        nb, block_shift(block), DELTA_I8};
+  return d;
+}
+
+// W [n_models, n_segs] as fp32 on base's device; it and the offsets must fit
+// the dynamic LDS the merge kernel caches them in: on their own, which is all
+// a dense store puts there, and for top-k behind its tiles
+Tensor merge_weights(const Tensor& W, const Tensor& base, const DeltaStore& d,
+                     int n_models, int n_segs) {
+  TORCH_CHECK(W.dim() == 2 && W.size(0) == n_models && W.size(1) == n_segs,
+              "W must be [n_models, n_segs]");
+  const DeltaStore dense{DELTA_F32};
+  TORCH_CHECK(dta_merge_shmem(dense, n_models, n_segs) <= DTA_MERGE_LDS_LIMIT,
+              "offsets + W ([", n_models, ", ", n_segs,
+              "]) do not fit the LDS budget of ", DTA_MERGE_LDS_LIMIT, " B");
+  if (d.kind == DELTA_TOPK)
+    TORCH_CHECK(dta_merge_shmem(d, n_models, n_segs) <= DTA_MERGE_LDS_LIMIT,
+                "topk merge: tiles + offsets + W do not fit the LDS budget "
+                "of ", DTA_MERGE_LDS_LIMIT, " B");
+  return W.to(base.device(), torch::kFloat32).contiguous();
+}
+
+void merge_impl(int takes, const Tensor& base, const Tensor& data,
+                const Tensor& scales, int64_t block, const Tensor& W,
+                const Tensor& offsets, Tensor& out) {
   const int64_t P = base.numel();
-  check_plane_f32(base, P, "base"); check_plane_f32(out, P, "out");
-  const int n_models = check_deltas_f32(deltas, P);
+  const bool aligned = takes != TAKES_F32;
+  check_plane(base, P, "base", aligned); check_plane(out, P, "out", aligned);
+  const DeltaStore d = delta_store(data, scales, block, P, takes);
+  const int n_models = int(data.size(0));
   const int n_segs = merge_n_segs(offsets);
-  auto Wc = merge_weights(W, base, n_models, n_segs);
+  auto Wc = merge_weights(W, base, d, n_models, n_segs);
   auto offs = merge_offsets(offsets, base);
-  launch_weighted_merge(base.data_ptr<float>(), deltas.data_ptr<float>(),
-                        Wc.data_ptr<float>(), offs.data_ptr<int64_t>(),
-                        n_models, n_segs, P, out.data_ptr<float>(), stream());
+  launch_weighted_merge(base.data_ptr<float>(), d, Wc.data_ptr<float>(),
+                        offs.data_ptr<int64_t>(), n_models, n_segs, P,
+                        out.data_ptr<float>(), stream());
 }
 
 // boundary-aligned chunk table for grad_W: [n_chunks, 3] int64 rows
@@ -660,118 +779,111 @@ Tensor grad_w_chunks(const Tensor& offsets, const Tensor& base, int n_segs) {
       .to(base.device());
 }
 
-// g: the bf16 or fp32 [P] gradient plane both grad_W entry points read
-bool check_grad_plane(const Tensor& g, int64_t P) {
+Tensor grad_w_impl(int takes, const Tensor& g, const Tensor& base,
+                   const Tensor& data, const Tensor& scales, int64_t block,
+                   const Tensor& merged, const Tensor& offsets) {
+  const int64_t P = base.numel();
+  const bool aligned = takes != TAKES_F32;
+  check_plane(base, P, "base", aligned);
+  check_plane(merged, P, "merged", aligned);
   const bool gb = g.scalar_type() == torch::kBFloat16;
   TORCH_CHECK(g.is_cuda() && g.is_contiguous() && g.numel() == P &&
                   (gb || g.scalar_type() == torch::kFloat32),
               "g must be a contiguous bf16/fp32 [P] GPU tensor");
-  return gb;
-}
-
-Tensor grad_merge_weights(Tensor g, Tensor base, Tensor deltas, Tensor merged,
-                          Tensor offsets) {
-  const int64_t P = base.numel();
-  check_plane_f32(base, P, "base"); check_plane_f32(merged, P, "merged");
-  const bool gb = check_grad_plane(g, P);
-  const int n_models = check_deltas_f32(deltas, P);
+  // the top-k kernel reads g an element per lane, like the fp32 one
+  if (aligned && delta_kind(data) != DELTA_TOPK)
+    TORCH_CHECK(aligned16(g), "g must be 16-byte aligned");
+  const DeltaStore d = delta_store(data, scales, block, P, takes);
+  const int n_models = int(data.size(0));
   const int n_segs = merge_n_segs(offsets);
   auto ch = grad_w_chunks(offsets, base, n_segs);
   const int n_chunks = int(ch.numel() / 3);
   auto gw = torch::zeros({n_models, n_segs},
                          base.options().dtype(torch::kFloat32));
-  launch_grad_merge_weights(g.data_ptr(), gb, base.data_ptr<float>(),
-                            deltas.data_ptr<float>(),
-                            merged.data_ptr<float>(),
-                            ch.data_ptr<int64_t>(), n_models, n_chunks, P,
-                            gw.data_ptr<float>(), n_segs, stream());
+  launch_grad_merge_weights(g.data_ptr(), gb, base.data_ptr<float>(), d,
+                            merged.data_ptr<float>(), ch.data_ptr<int64_t>(),
+                            n_models, n_chunks, P, gw.data_ptr<float>(),
+                            n_segs, stream());
   return gw;
 }
 
-// ---- packed deltas (bf16, or int8 codes + scales) ---------------------------
-bool aligned16(const Tensor& t) {
-  return reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0;
+// ---- the exports: which forms each takes --------------------------------------
+void weighted_merge(Tensor base, Tensor deltas, Tensor W, Tensor offsets,
+                    Tensor out) {
+  merge_impl(TAKES_F32, base, deltas, Tensor(), 0, W, offsets, out);
+}
+void weighted_merge_packed(Tensor base, Tensor data, Tensor scales,
+                           int64_t block, Tensor W, Tensor offsets,
+                           Tensor out) {
+  merge_impl(TAKES_PACKED | TAKES_TOPK, base, data, scales, block, W, offsets,
+             out);
+}
+Tensor grad_merge_weights(Tensor g, Tensor base, Tensor deltas, Tensor merged,
+                          Tensor offsets) {
+  return grad_w_impl(TAKES_F32, g, base, deltas, Tensor(), 0, merged, offsets);
+}
+Tensor grad_merge_weights_packed(Tensor g, Tensor base, Tensor data,
+                                 Tensor scales, int64_t block, Tensor merged,
+                                 Tensor offsets) {
+  return grad_w_impl(TAKES_PACKED | TAKES_TOPK, g, base, data, scales, block,
+                     merged, offsets);
+}
+// an fp32 row has no entry here: it is a plain axpy
+void axpy_packed(Tensor w, Tensor data, Tensor scales, int64_t block,
+                 int64_t row, double alpha) {
+  const int64_t P = w.numel();
+  check_plane(w, P, "w");
+  const DeltaStore d =
+      delta_store(data, scales, block, P, TAKES_PACKED | TAKES_TOPK);
+  TORCH_CHECK(row >= 0 && row < data.size(0), "row out of range");
+  launch_axpy_row(w.data_ptr<float>(), d, int(row), float(alpha), P,
+                  stream());
 }
 
-// data [N, P] bf16 with scales empty, or data [N, nb*block] int8 with scales
-// [N, nb] fp32; P is the length of a dequantised row.
-PackedView packed_view(const Tensor& data, const Tensor& scales, int64_t P,
-                       int64_t block) {
-  TORCH_CHECK(data.is_cuda() && data.dim() == 2 && data.is_contiguous(),
-              "packed data must be a contiguous [N, cols] GPU tensor");
-  TORCH_CHECK(data.size(0) >= 1 && data.size(0) <= DTA_MERGE_MAX_MODELS,
-              "packed deltas: 1 <= n_models <= ", DTA_MERGE_MAX_MODELS);
-  TORCH_CHECK(aligned16(data), "packed data must be 16-byte aligned");
-  TORCH_CHECK(P >= 1, "packed deltas: empty plane");
-  if (data.scalar_type() == torch::kBFloat16) {
-    TORCH_CHECK(data.size(1) == P, "bf16 deltas must be [N, P]");
-    return PackedView{data.data_ptr(), nullptr, P, 0, 0, DELTA_BF16};
+// ---- robust merge (merge.hip, trimmed_merge_k) -------------------------------
+int trimmed_kind(const Tensor& data) {
+  const int kind = delta_kind(data);
+  TORCH_CHECK(kind >= 0 && kind != DELTA_TOPK,
+              "trimmed_merge: deltas must be fp32, bf16 or int8 "
+              "(top-k deltas have no coordinate-wise median)");
+  return kind;
+}
+// data [N, P] fp32 (scales empty, block unused), or bf16 / int8 + scales as
+// the packed merge takes them. out [P] fp32 is written; outside, where given,
+// is an int64 [N] tensor the counts are ADDED to (the caller zero-fills it).
+void trimmed_merge(Tensor base, Tensor data, Tensor scales, int64_t block,
+                   int64_t trim, Tensor out, OptTensor outside) {
+  const int64_t P = base.numel();
+  TORCH_CHECK(data.dim() == 2, "trimmed_merge: deltas must be [N, cols]");
+  const int n_models = merge_n_models(data.size(0));
+  TORCH_CHECK(trim >= 0 && 2 * trim < n_models,
+              "trimmed_merge: need 0 <= 2 * trim < n_models, got trim ", trim,
+              " for ", n_models, " deltas");
+  trimmed_kind(data);   // top-k is refused before the planes are looked at
+  check_plane(base, P, "base", false); check_plane(out, P, "out", false);
+  const DeltaStore d =
+      delta_store(data, scales, block, P, TAKES_F32 | TAKES_PACKED);
+  if (dta_trimmed_vec(d.kind, n_models, P) == 4)
+    TORCH_CHECK(aligned16(base) && aligned16(out) && aligned16(data),
+                "trimmed_merge: base, out and the deltas must be 16-byte "
+                "aligned");
+  int64_t* cnt = nullptr;
+  if (outside.has_value() && outside->defined()) {
+    TORCH_CHECK(outside->is_cuda() && outside->is_contiguous() &&
+                    outside->scalar_type() == torch::kInt64 &&
+                    outside->dim() == 1 && outside->numel() == n_models,
+                "outside must be a contiguous int64 [N] GPU tensor");
+    cnt = outside->data_ptr<int64_t>();
   }
-  TORCH_CHECK(data.scalar_type() == torch::kInt8,
-              "packed data must be bf16 or int8");
-  TORCH_CHECK(block >= DTA_QUANT_MIN_BLOCK && block <= DTA_QUANT_MAX_BLOCK &&
-                  (block & (block - 1)) == 0,
-              "block must be a power of two in [", DTA_QUANT_MIN_BLOCK, ", ",
-              DTA_QUANT_MAX_BLOCK, "]");
-  const int64_t nb = (P + block - 1) / block;
-  TORCH_CHECK(data.size(1) == nb * block,
-              "int8 codes must be [N, nb*block], nb = ceil(P / block)");
-  check_f32(scales, "scales");
-  TORCH_CHECK(scales.dim() == 2 && scales.size(0) == data.size(0) &&
-                  scales.size(1) == nb, "scales must be [N, nb]");
-  int shift = 0;
-  while ((int64_t(1) << shift) < block) ++shift;
-  return PackedView{data.data_ptr(), scales.data_ptr<float>(), nb * block, nb,
-                    shift, DELTA_I8};
+  launch_trimmed_merge(base.data_ptr<float>(), d, n_models, int(trim), P,
+                       out.data_ptr<float>(), cnt, stream());
 }
-
-void check_plane(const Tensor& t, int64_t P, const char* name) {
-  check_f32(t, name);
-  TORCH_CHECK(t.numel() == P, name, " must have P elements");
-  TORCH_CHECK(aligned16(t), name, " must be 16-byte aligned");
-}
-
-// ---- top-k deltas ----------------------------------------------------------
-// The fourth wire form has no export names of its own: the packed entry
-// points below take int32 entries as they take bf16 or int8 data (k is
-// data.size(1) / nb), and quantize_int8 makes them when topk_k > 0.
-bool is_topk(const Tensor& data) {
-  return data.scalar_type() == torch::kInt32;
-}
-// entries per block of int32 [N, nb*k] data; topk_view checks the rest
-int64_t topk_k_of(const Tensor& data, int64_t P, int64_t block) {
-  TORCH_CHECK(data.dim() == 2 && P >= 1 && block >= 1,
-              "topk entries must be [N, nb*k]");
-  return data.size(1) / ((P + block - 1) / block);
-}
-// the format's limits (comm.check_topk_format); returns nb
-int64_t check_topk_format(int64_t P, int64_t k, int64_t block) {
-  TORCH_CHECK(P >= 1, "topk deltas: empty plane");
-  TORCH_CHECK(block >= DTA_TOPK_MIN_BLOCK && block <= DTA_TOPK_MAX_BLOCK &&
-                  (block & (block - 1)) == 0,
-              "topk block must be a power of two in [", DTA_TOPK_MIN_BLOCK,
-              ", ", DTA_TOPK_MAX_BLOCK, "]");
-  TORCH_CHECK(k >= 4 && k % 4 == 0 && k <= block / 4,
-              "topk k must be a multiple of 4 in [4, block / 4]");
-  const int64_t nb = (P + block - 1) / block;
-  TORCH_CHECK(nb < (int64_t(1) << 31), "too many top-k blocks");
-  return nb;
-}
-
-// data: int32 [N, nb*k] entries of N rows of a P-element plane
-TopkView topk_view(const Tensor& data, int64_t P, int64_t k, int64_t block) {
-  const int64_t nb = check_topk_format(P, k, block);
-  TORCH_CHECK(data.is_cuda() && data.dim() == 2 && data.is_contiguous() &&
-                  data.scalar_type() == torch::kInt32,
-              "topk entries must be a contiguous int32 [N, nb*k] GPU tensor");
-  TORCH_CHECK(data.size(0) >= 1 && data.size(0) <= DTA_MERGE_MAX_MODELS,
-              "topk deltas: 1 <= n_models <= ", DTA_MERGE_MAX_MODELS);
-  TORCH_CHECK(data.size(1) == nb * k,
-              "topk entries must be [N, nb*k], nb = ceil(P / block)");
-  TORCH_CHECK(aligned16(data), "topk entries must be 16-byte aligned");
-  int shift = 0;
-  while ((int64_t(1) << shift) < block) ++shift;
-  return TopkView{data.data_ptr<int>(), nb * k, shift, int(k)};
+// elements one sweep of the launcher's capped grid covers (tests size a case
+// that takes the grid-stride loop round a second time from it)
+int64_t trimmed_sweep(Tensor data, int64_t P) {
+  TORCH_CHECK(data.dim() == 2, "trimmed_merge: deltas must be [N, cols]");
+  return dta_trimmed_sweep(trimmed_kind(data), merge_n_models(data.size(0)),
+                           P);
 }
 
 // entries [nb*k] of (x - base) + residual_in; base / residual_in /
@@ -802,162 +914,6 @@ Tensor topk_compress(Tensor x, Tensor base, Tensor residual_in,
   return entries;
 }
 
-void weighted_merge_topk(Tensor base, Tensor data, int64_t k, int64_t block,
-                         Tensor W, Tensor offsets, Tensor out) {
-  const int64_t P = base.numel();
-  check_plane(base, P, "base"); check_plane(out, P, "out");
-  const TopkView d = topk_view(data, P, k, block);
-  const int n_models = merge_n_models(data.size(0));
-  const int n_segs = merge_n_segs(offsets);
-  auto Wc = merge_weights(W, base, n_models, n_segs);
-  TORCH_CHECK(dta_topk_merge_shmem(n_models, n_segs, int(block)) <=
-                  DTA_MERGE_LDS_LIMIT,
-              "topk merge: tiles + offsets + W do not fit the LDS budget of ",
-              DTA_MERGE_LDS_LIMIT, " B");
-  auto offs = merge_offsets(offsets, base);
-  launch_weighted_merge_topk(base.data_ptr<float>(), d, Wc.data_ptr<float>(),
-                             offs.data_ptr<int64_t>(), n_models, n_segs, P,
-                             out.data_ptr<float>(), stream());
-}
-
-Tensor grad_merge_weights_topk(Tensor g, Tensor base, Tensor data, int64_t k,
-                               int64_t block, Tensor merged, Tensor offsets) {
-  const int64_t P = base.numel();
-  check_plane(base, P, "base"); check_plane(merged, P, "merged");
-  const bool gb = check_grad_plane(g, P);
-  const TopkView d = topk_view(data, P, k, block);
-  const int n_models = merge_n_models(data.size(0));
-  const int n_segs = merge_n_segs(offsets);
-  auto ch = grad_w_chunks(offsets, base, n_segs);
-  const int n_chunks = int(ch.numel() / 3);
-  auto gw = torch::zeros({n_models, n_segs},
-                         base.options().dtype(torch::kFloat32));
-  launch_grad_merge_weights_topk(g.data_ptr(), gb, base.data_ptr<float>(), d,
-                                 merged.data_ptr<float>(),
-                                 ch.data_ptr<int64_t>(), n_models, n_chunks,
-                                 P, gw.data_ptr<float>(), n_segs, stream());
-  return gw;
-}
-
-void axpy_topk(Tensor w, Tensor data, int64_t k, int64_t block, int64_t row,
-               double alpha) {
-  const int64_t P = w.numel();
-  check_plane(w, P, "w");
-  const TopkView d = topk_view(data, P, k, block);
-  TORCH_CHECK(row >= 0 && row < data.size(0), "row out of range");
-  launch_axpy_topk(w.data_ptr<float>(), d, int(row), float(alpha), P,
-                   stream());
-}
-
-void weighted_merge_packed(Tensor base, Tensor data, Tensor scales,
-                           int64_t block, Tensor W, Tensor offsets,
-                           Tensor out) {
-  const int64_t P = base.numel();
-  if (is_topk(data))
-    return weighted_merge_topk(base, data, topk_k_of(data, P, block), block,
-                               W, offsets, out);
-  check_plane(base, P, "base"); check_plane(out, P, "out");
-  const PackedView d = packed_view(data, scales, P, block);
-  const int n_models = merge_n_models(data.size(0));
-  const int n_segs = merge_n_segs(offsets);
-  auto Wc = merge_weights(W, base, n_models, n_segs);
-  auto offs = merge_offsets(offsets, base);
-  launch_weighted_merge_packed(base.data_ptr<float>(), d,
-                               Wc.data_ptr<float>(),
-                               offs.data_ptr<int64_t>(), n_models, n_segs, P,
-                               out.data_ptr<float>(), stream());
-}
-
-Tensor grad_merge_weights_packed(Tensor g, Tensor base, Tensor data,
-                                 Tensor scales, int64_t block, Tensor merged,
-                                 Tensor offsets) {
-  const int64_t P = base.numel();
-  if (is_topk(data))
-    return grad_merge_weights_topk(g, base, data, topk_k_of(data, P, block),
-                                   block, merged, offsets);
-  check_plane(base, P, "base"); check_plane(merged, P, "merged");
-  const bool gb = check_grad_plane(g, P);
-  TORCH_CHECK(aligned16(g), "g must be 16-byte aligned");
-  const PackedView d = packed_view(data, scales, P, block);
-  const int n_models = merge_n_models(data.size(0));
-  const int n_segs = merge_n_segs(offsets);
-  auto ch = grad_w_chunks(offsets, base, n_segs);
-  const int n_chunks = int(ch.numel() / 3);
-  auto gw = torch::zeros({n_models, n_segs},
-                         base.options().dtype(torch::kFloat32));
-  launch_grad_merge_weights_packed(g.data_ptr(), gb, base.data_ptr<float>(),
-                                   d, merged.data_ptr<float>(),
-                                   ch.data_ptr<int64_t>(), n_models, n_chunks,
-                                   P, gw.data_ptr<float>(), n_segs, stream());
-  return gw;
-}
-
-void axpy_packed(Tensor w, Tensor data, Tensor scales, int64_t block,
-                 int64_t row, double alpha) {
-  const int64_t P = w.numel();
-  if (is_topk(data))
-    return axpy_topk(w, data, topk_k_of(data, P, block), block, row, alpha);
-  check_plane(w, P, "w");
-  const PackedView d = packed_view(data, scales, P, block);
-  TORCH_CHECK(row >= 0 && row < data.size(0), "row out of range");
-  launch_axpy_packed(w.data_ptr<float>(), d, int(row), float(alpha), P,
-                     stream());
-}
-
-// ---- robust merge (merge.hip, trimmed_merge_k) -------------------------------
-int trimmed_kind(const Tensor& data) {
-  switch (data.scalar_type()) {
-    case torch::kFloat32: return DELTA_F32;
-    case torch::kBFloat16: return DELTA_BF16;
-    case torch::kInt8: return DELTA_I8;
-    default:
-      TORCH_CHECK(false, "trimmed_merge: deltas must be fp32, bf16 or int8 "
-                         "(top-k deltas have no coordinate-wise median)");
-  }
-}
-// data [N, P] fp32 (scales empty, block unused), or bf16 / int8 + scales as
-// the packed merge takes them. out [P] fp32 is written; outside, where given,
-// is an int64 [N] tensor the counts are ADDED to (the caller zero-fills it).
-void trimmed_merge(Tensor base, Tensor data, Tensor scales, int64_t block,
-                   int64_t trim, Tensor out, OptTensor outside) {
-  const int64_t P = base.numel();
-  TORCH_CHECK(data.dim() == 2, "trimmed_merge: deltas must be [N, cols]");
-  const int n_models = merge_n_models(data.size(0));
-  TORCH_CHECK(trim >= 0 && 2 * trim < n_models,
-              "trimmed_merge: need 0 <= 2 * trim < n_models, got trim ", trim,
-              " for ", n_models, " deltas");
-  const int kind = trimmed_kind(data);
-  check_plane_f32(base, P, "base"); check_plane_f32(out, P, "out");
-  PackedView d;
-  if (kind == DELTA_F32) {
-    check_deltas_f32(data, P);
-    d = PackedView{data.data_ptr(), nullptr, P, 0, 0, DELTA_F32};
-  } else {
-    d = packed_view(data, scales, P, block);
-  }
-  if (dta_trimmed_vec(kind, n_models, P) == 4)
-    TORCH_CHECK(aligned16(base) && aligned16(out) && aligned16(data),
-                "trimmed_merge: base, out and the deltas must be 16-byte "
-                "aligned");
-  int64_t* cnt = nullptr;
-  if (outside.has_value() && outside->defined()) {
-    TORCH_CHECK(outside->is_cuda() && outside->is_contiguous() &&
-                    outside->scalar_type() == torch::kInt64 &&
-                    outside->dim() == 1 && outside->numel() == n_models,
-                "outside must be a contiguous int64 [N] GPU tensor");
-    cnt = outside->data_ptr<int64_t>();
-  }
-  launch_trimmed_merge(base.data_ptr<float>(), d, n_models, int(trim), P,
-                       out.data_ptr<float>(), cnt, stream());
-}
-// elements one sweep of the launcher's capped grid covers (tests size a case
-// that takes the grid-stride loop round a second time from it)
-int64_t trimmed_sweep(Tensor data, int64_t P) {
-  TORCH_CHECK(data.dim() == 2, "trimmed_merge: deltas must be [N, cols]");
-  return dta_trimmed_sweep(trimmed_kind(data), merge_n_models(data.size(0)),
-                           P);
-}
-
 // (codes [nb*block] int8, scales [nb] fp32) of x - base, or of x when base
 // is empty. topk_k > 0: the top-k form of the same delta instead, {entries
 // [nb*topk_k] int32} of (x - base) + residual_in, with the remainder
@@ -977,10 +933,7 @@ std::vector<Tensor> quantize_int8(Tensor x, Tensor base, int64_t block,
   const int64_t P = x.numel();
   TORCH_CHECK(P >= 1, "quantize_int8: empty input");
   TORCH_CHECK(aligned16(x), "x must be 16-byte aligned");
-  TORCH_CHECK(block >= DTA_QUANT_MIN_BLOCK && block <= DTA_QUANT_MAX_BLOCK &&
-                  (block & (block - 1)) == 0,
-              "block must be a power of two in [", DTA_QUANT_MIN_BLOCK, ", ",
-              DTA_QUANT_MAX_BLOCK, "]");
+  check_quant_block(block);
   const float* bp = nullptr;
   if (base.numel()) {
     check_plane(base, P, "base");

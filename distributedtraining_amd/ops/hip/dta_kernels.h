@@ -150,26 +150,24 @@ inline int dta_gelu_colsum_stripes(int64_t rows, int cols) {
 }
 
 // ---- merge plane ----------------------------------------------------------
-void launch_weighted_merge(const float* base, const float* deltas,  // [N,P]
-                           const float* W,                          // [N,S]
-                           const int64_t* offsets, int n_models, int n_segs,
-                           int64_t P, float* out, hipStream_t s);
-// chunks: [n_chunks,3] int64 (start,end,seg) rows, none crossing a segment
-void launch_grad_merge_weights(const void* g, bool g_is_bf16,
-                               const float* base, const float* deltas,
-                               const float* merged, const int64_t* chunks,
-                               int n_models, int n_chunks, int64_t P,
-                               float* grad_w,  // [N,S] pre-zeroed
-                               int n_segs, hipStream_t s);
-// Gathered deltas kept in their wire form. bf16: data [N, ld = P]. int8:
-// data [N, ld = nb*block] codes, scales [N, nb] fp32, block == 1 << shift;
-// element e of row i is float(code) * scales[i, e >> shift], one rounded
-// fp32 multiply. The packed kernels produce what the fp32 ones produce on
-// the dequantised rows, bit for bit (grad_W keeps the fp32 kernel's
-// summation order). Merge and axpy read 4 elements per lane: base/out/w must
-// be 16 B aligned and data 8 B; bf16 with P % 4 != 0 falls back to one
-// element per lane.
-enum DeltaKind { DELTA_F32 = 0, DELTA_BF16 = 1, DELTA_I8 = 2 };
+// Gathered deltas stay in the form they were gathered in; DeltaStore says
+// which of the four, and every consumer below takes it.
+//   fp32  packed.data [N, ld = P].
+//   bf16  packed.data [N, ld = P].
+//   int8  packed.data [N, ld = nb*block] codes, packed.scales [N, nb] fp32,
+//         block == 1 << shift; element e of row i is float(code) *
+//         scales[i, e >> shift], one rounded fp32 multiply.
+//   topk  topk.data [N, ld = nb*k] entries (idx << 16 | bf16 bits), k per
+//         block of 1 << shift elements; entries whose element lies past P are
+//         skipped.
+// The bf16, int8 and topk kernels produce what the fp32 kernel produces on
+// the dequantised (densified) rows, bit for bit; grad_W keeps the fp32
+// kernel's summation order. Alignment, by form: fp32 merge and grad_W read
+// one element per lane and ask for none. bf16 and int8 merge and axpy read 4
+// elements per lane: base/out/w must be 16 B aligned and data 8 B; bf16 with
+// P % 4 != 0 falls back to one element per lane. topk: base/out/w and data
+// 16 B aligned.
+enum DeltaKind { DELTA_F32 = 0, DELTA_BF16 = 1, DELTA_I8 = 2, DELTA_TOPK = 3 };
 struct PackedView {
   const void* data;
   const float* scales;   // int8 only
@@ -178,26 +176,44 @@ struct PackedView {
   int shift;             // log2(block) (int8 only)
   int kind;              // DeltaKind
 };
+struct TopkView {
+  const int* data;
+  int64_t ld;
+  int shift;
+  int k;
+};
+struct DeltaStore {
+  int kind;              // DeltaKind: DELTA_TOPK reads topk, the rest packed
+  PackedView packed;
+  TopkView topk;
+};
 constexpr int DTA_MERGE_MAX_MODELS = 32;   // miners per node (8 GPUs typical)
-constexpr size_t DTA_MERGE_LDS_LIMIT = 64 * 1024;   // offsets + W, per block
-// dynamic LDS weighted_merge needs for its offsets and W cache
-size_t dta_merge_shmem(int n_models, int n_segs);
-void launch_weighted_merge_packed(const float* base, const PackedView& d,
-                                  const float* W, const int64_t* offsets,
-                                  int n_models, int n_segs, int64_t P,
-                                  float* out, hipStream_t s);
-void launch_grad_merge_weights_packed(const void* g, bool g_is_bf16,
-                                      const float* base, const PackedView& d,
-                                      const float* merged,
-                                      const int64_t* chunks, int n_models,
-                                      int n_chunks, int64_t P, float* grad_w,
-                                      int n_segs, hipStream_t s);
+constexpr size_t DTA_MERGE_LDS_LIMIT = 64 * 1024;   // per block
+// dynamic LDS of weighted_merge: its offsets and W cache, and for topk two
+// tiles of min(block, 4096) fp32 in front of them
+size_t dta_merge_shmem(const DeltaStore& d, int n_models, int n_segs);
+void launch_weighted_merge(const float* base, const DeltaStore& d,  // N rows
+                           const float* W,                          // [N,S]
+                           const int64_t* offsets, int n_models, int n_segs,
+                           int64_t P, float* out, hipStream_t s);
+// chunks: [n_chunks,3] int64 (start,end,seg) rows, none crossing a segment
+void launch_grad_merge_weights(const void* g, bool g_is_bf16,
+                               const float* base, const DeltaStore& d,
+                               const float* merged, const int64_t* chunks,
+                               int n_models, int n_chunks, int64_t P,
+                               float* grad_w,  // [N,S] pre-zeroed
+                               int n_segs, hipStream_t s);
+// w += alpha * row `row` of d, dequantised in registers. d: bf16, int8 or
+// topk (an fp32 row is a plain launch_axpy). topk touches only the elements
+// on the row's support, so it equals the dense kernel as numbers.
+void launch_axpy_row(float* w, const DeltaStore& d, int row, float alpha,
+                     int64_t P, hipStream_t s);
 // Robust merge: out[e] = base[e] + mean of the sorted positions trim ..
 // n_models-1-trim of the n_models values delta_i[e] (0 <= 2*trim < n_models;
 // trim = (n_models-1)/2 is the median), and outside[i] += the number of
 // elements at which row i lies strictly outside that kept interval. The
-// order is total: -inf < .. < -0 < +0 < .. < +inf < NaN. d: fp32 (kind
-// DELTA_F32, data [N, ld = P]), bf16 or int8. Bit-equal to the CPU path of
+// order is total: -inf < .. < -0 < +0 < .. < +inf < NaN. d: fp32, bf16 or
+// int8 (topk has no coordinate-wise median). Bit-equal to the CPU path of
 // ops.trimmed_merge, independent of the row order. outside: int64
 // [n_models], zero-filled by the caller, integer atomics only; null: no
 // counts. The rows are padded to dta_trimmed_pad(n_models) sort keys per
@@ -212,14 +228,11 @@ inline int dta_trimmed_vec(int kind, int n_models, int64_t P) {
   // as the packed merge: a row start must be aligned, int8 rows are padded
   return (kind == DELTA_I8 || P % 4 == 0) ? 4 : 1;
 }
-void launch_trimmed_merge(const float* base, const PackedView& d,
+void launch_trimmed_merge(const float* base, const DeltaStore& d,
                           int n_models, int trim, int64_t P, float* out,
                           int64_t* outside, hipStream_t s);
 // elements one sweep of its capped grid covers; more take the grid-stride loop
 int64_t dta_trimmed_sweep(int kind, int n_models, int64_t P);
-// w += alpha * row `row` of d, dequantised in registers
-void launch_axpy_packed(float* w, const PackedView& d, int row, float alpha,
-                        int64_t P, hipStream_t s);
 // Blockwise int8 of d = w - base (base null: of w), bit-equal to
 // comm.quantize_blockwise_int8 on the CPU. codes [nb*block], scales [nb],
 // nb = ceil(P / block); block a power of two in [DTA_QUANT_MIN_BLOCK,
@@ -241,31 +254,6 @@ void launch_delta_topk(const float* w, const float* base,
                        const float* residual_in, float* residual_out,
                        int64_t P, int block, int k, int64_t nb, int* entries,
                        hipStream_t s);
-// Gathered top-k deltas: data [N, ld = nb*k] entries, block == 1 << shift.
-// Entries whose element lies past P are skipped. Each consumer produces what
-// its fp32 kernel produces on the densified rows, bit for bit (axpy: as
-// numbers; it touches only the elements on the support). base/out/w 16 B
-// aligned.
-struct TopkView {
-  const int* data;
-  int64_t ld;
-  int shift;
-  int k;
-};
-// dynamic LDS of the merge: two tiles of min(block, 4096) fp32 + offsets + W
-size_t dta_topk_merge_shmem(int n_models, int n_segs, int block);
-void launch_weighted_merge_topk(const float* base, const TopkView& d,
-                                const float* W, const int64_t* offsets,
-                                int n_models, int n_segs, int64_t P,
-                                float* out, hipStream_t s);
-void launch_grad_merge_weights_topk(const void* g, bool g_is_bf16,
-                                    const float* base, const TopkView& d,
-                                    const float* merged,
-                                    const int64_t* chunks, int n_models,
-                                    int n_chunks, int64_t P, float* grad_w,
-                                    int n_segs, hipStream_t s);
-void launch_axpy_topk(float* w, const TopkView& d, int row, float alpha,
-                      int64_t P, hipStream_t s);
 
 // ---- norms ----------------------------------------------------------------
 // dγ/dβ partial-panel geometry: for cols <= 1024 the partials come from

@@ -25,6 +25,10 @@
 // with an error-feedback residual). delta_at cannot express it; its three
 // consumers are kernels of their own further down and hold the same
 // contract, the fp32 kernel's bits on the densified rows.
+//
+// The host side sees one description of all four, DeltaStore
+// (dta_kernels.h), and one launcher per consumer at the end of this file
+// picks the kernel, grid and LDS from it.
 #include "dta_common.h"
 #include "dta_kernels.h"
 
@@ -979,49 +983,105 @@ __global__ void axpy_topk_k(float* __restrict__ w, TopkArgs a, int row,
   }
 }
 
-size_t merge_shmem(int n_models, int n_segs) {
-  return (n_segs + 1) * sizeof(int64_t) + 8 +
-         size_t(n_models) * n_segs * sizeof(float);
-}
-
 // V == 4 needs every row start 8 B aligned; int8 rows are whole blocks
 bool packed_vec4(const PackedView& d, int64_t P) {
   return d.kind == DELTA_I8 || P % 4 == 0;
 }
 
-}  // namespace
-
-size_t dta_merge_shmem(int n_models, int n_segs) {
-  return merge_shmem(n_models, n_segs);
+TopkArgs topk_args(const TopkView& d) {
+  const int block = 1 << d.shift;
+  return TopkArgs{d.data, d.ld, d.shift, d.k,
+                  block < TOPK_TILE ? block : TOPK_TILE};
 }
 
-void launch_weighted_merge(const float* base, const float* deltas,
+}  // namespace
+
+// ---- launchers: one per consumer, each a function of the store ---------------
+size_t dta_merge_shmem(const DeltaStore& d, int n_models, int n_segs) {
+  const size_t tables = (n_segs + 1) * sizeof(int64_t) + 8 +
+                        size_t(n_models) * n_segs * sizeof(float);
+  if (d.kind != DELTA_TOPK) return tables;
+  return 2 * sizeof(float) * size_t(topk_args(d.topk).tile) + tables;
+}
+
+void launch_weighted_merge(const float* base, const DeltaStore& d,
                            const float* W, const int64_t* offsets,
                            int n_models, int n_segs, int64_t P, float* out,
                            hipStream_t s) {
+  const size_t shmem = dta_merge_shmem(d, n_models, n_segs);
+  if (d.kind == DELTA_TOPK) {
+    const TopkArgs a = topk_args(d.topk);
+    const int64_t n_tiles = (P + a.tile - 1) / a.tile;
+    const int grid =
+        int(n_tiles < MAX_RESIDENT_BLOCKS ? n_tiles : MAX_RESIDENT_BLOCKS);
+    weighted_merge_topk_k<<<grid, TOPK_THREADS, shmem, s>>>(
+        base, a, W, offsets, n_models, n_segs, P, out);
+    return;
+  }
   const int block = 256;
-  const int grid = elementwise_grid(P, block, 1);
-  const PackedView d{deltas, nullptr, P, 0, 0, DELTA_F32};
-  weighted_merge_k<DELTA_F32, 1>
-      <<<grid, block, merge_shmem(n_models, n_segs), s>>>(
-          base, DELTA_ARGS(d), W, offsets, n_models, n_segs, P, out);
-}
-
-void launch_weighted_merge_packed(const float* base, const PackedView& d,
-                                  const float* W, const int64_t* offsets,
-                                  int n_models, int n_segs, int64_t P,
-                                  float* out, hipStream_t s) {
-  const int block = 256;
-  const size_t shmem = merge_shmem(n_models, n_segs);
-  const bool v4 = packed_vec4(d, P);
+  // fp32 rows are read an element per lane
+  const bool v4 = d.kind != DELTA_F32 && packed_vec4(d.packed, P);
   const int grid = elementwise_grid(P, block, v4 ? 4 : 1);
 #define MERGE_GO(KIND, V)                                                   \
   weighted_merge_k<KIND, V><<<grid, block, shmem, s>>>(                     \
-      base, DELTA_ARGS(d), W, offsets, n_models, n_segs, P, out)
-  if (d.kind == DELTA_I8) MERGE_GO(DELTA_I8, 4);
+      base, DELTA_ARGS(d.packed), W, offsets, n_models, n_segs, P, out)
+  if (d.kind == DELTA_F32) MERGE_GO(DELTA_F32, 1);
+  else if (d.kind == DELTA_I8) MERGE_GO(DELTA_I8, 4);
   else if (v4) MERGE_GO(DELTA_BF16, 4);
   else MERGE_GO(DELTA_BF16, 1);
 #undef MERGE_GO
+}
+
+void launch_grad_merge_weights(const void* g, bool g_is_bf16,
+                               const float* base, const DeltaStore& d,
+                               const float* merged, const int64_t* chunks,
+                               int n_models, int n_chunks, int64_t P,
+                               float* grad_w, int n_segs, hipStream_t s) {
+  dim3 grid(n_chunks, n_models);
+  if (d.kind == DELTA_TOPK) {
+    const TopkArgs a = topk_args(d.topk);
+    const size_t shmem = 2 * sizeof(float) * size_t(a.tile);
+    if (g_is_bf16)
+      grad_w_topk_k<true><<<grid, GW_THREADS, shmem, s>>>(
+          g, base, a, merged, chunks, n_segs, P, grad_w);
+    else
+      grad_w_topk_k<false><<<grid, GW_THREADS, shmem, s>>>(
+          g, base, a, merged, chunks, n_segs, P, grad_w);
+    return;
+  }
+#define GRADW_GO(KIND, WORD)                                                \
+  do {                                                                      \
+    if (g_is_bf16)                                                          \
+      grad_w_k<true, KIND, WORD><<<grid, GW_THREADS, 0, s>>>(               \
+          g, base, DELTA_ARGS(d.packed), merged, chunks, n_segs, P, grad_w); \
+    else                                                                    \
+      grad_w_k<false, KIND, WORD><<<grid, GW_THREADS, 0, s>>>(              \
+          g, base, DELTA_ARGS(d.packed), merged, chunks, n_segs, P, grad_w); \
+  } while (0)
+  if (d.kind == DELTA_F32) GRADW_GO(DELTA_F32, false);
+  else if (d.kind == DELTA_I8) GRADW_GO(DELTA_I8, true);
+  else if ((int64_t(n_models) * P) % 2 == 0) GRADW_GO(DELTA_BF16, true);
+  else GRADW_GO(DELTA_BF16, false);   // see delta_at
+#undef GRADW_GO
+}
+
+void launch_axpy_row(float* w, const DeltaStore& d, int row, float alpha,
+                     int64_t P, hipStream_t s) {
+  const int block = 256;
+  if (d.kind == DELTA_TOPK) {
+    const int grid = elementwise_grid(d.topk.ld, block, 4);
+    axpy_topk_k<<<grid, block, 0, s>>>(w, topk_args(d.topk), row, alpha, P);
+    return;
+  }
+  const bool v4 = packed_vec4(d.packed, P);
+  const int grid = elementwise_grid(P, block, v4 ? 4 : 1);
+#define AXPY_GO(KIND, V)                                                    \
+  axpy_packed_k<KIND, V><<<grid, block, 0, s>>>(                            \
+      w, DELTA_ARGS(d.packed), row, alpha, P)
+  if (d.kind == DELTA_I8) AXPY_GO(DELTA_I8, 4);
+  else if (v4) AXPY_GO(DELTA_BF16, 4);
+  else AXPY_GO(DELTA_BF16, 1);
+#undef AXPY_GO
 }
 
 int64_t dta_trimmed_sweep(int kind, int n_models, int64_t P) {
@@ -1029,7 +1089,7 @@ int64_t dta_trimmed_sweep(int kind, int n_models, int64_t P) {
          dta_trimmed_vec(kind, n_models, P);
 }
 
-void launch_trimmed_merge(const float* base, const PackedView& d,
+void launch_trimmed_merge(const float* base, const DeltaStore& d,
                           int n_models, int trim, int64_t P, float* out,
                           int64_t* outside, hipStream_t s) {
   const int np = dta_trimmed_pad(n_models);
@@ -1038,7 +1098,7 @@ void launch_trimmed_merge(const float* base, const PackedView& d,
   auto* cnt = reinterpret_cast<unsigned long long*>(outside);
 #define TRIM_GO(KIND, NP, V)                                                \
   trimmed_merge_k<KIND, NP, V><<<grid, TRIM_THREADS, 0, s>>>(               \
-      base, DELTA_ARGS(d), n_models, trim, P, out, cnt)
+      base, DELTA_ARGS(d.packed), n_models, trim, P, out, cnt)
 #define TRIM_NP(KIND, V)                                                    \
   do {                                                                      \
     if (np == 4) TRIM_GO(KIND, 4, V);                                       \
@@ -1061,60 +1121,6 @@ void launch_trimmed_merge(const float* base, const PackedView& d,
 #undef TRIM_GO
 }
 
-void launch_grad_merge_weights(const void* g, bool g_is_bf16,
-                               const float* base, const float* deltas,
-                               const float* merged, const int64_t* chunks,
-                               int n_models, int n_chunks, int64_t P,
-                               float* grad_w, int n_segs, hipStream_t s) {
-  dim3 grid(n_chunks, n_models);
-  const PackedView d{deltas, nullptr, P, 0, 0, DELTA_F32};
-  if (g_is_bf16)
-    grad_w_k<true, DELTA_F32><<<grid, GW_THREADS, 0, s>>>(
-        g, base, DELTA_ARGS(d), merged, chunks, n_segs, P, grad_w);
-  else
-    grad_w_k<false, DELTA_F32><<<grid, GW_THREADS, 0, s>>>(
-        g, base, DELTA_ARGS(d), merged, chunks, n_segs, P, grad_w);
-}
-
-void launch_grad_merge_weights_packed(const void* g, bool g_is_bf16,
-                                      const float* base, const PackedView& d,
-                                      const float* merged,
-                                      const int64_t* chunks, int n_models,
-                                      int n_chunks, int64_t P, float* grad_w,
-                                      int n_segs, hipStream_t s) {
-  dim3 grid(n_chunks, n_models);
-#define GRADW_GO(GB, KIND, WORD)                                            \
-  grad_w_k<GB, KIND, WORD><<<grid, GW_THREADS, 0, s>>>(                     \
-      g, base, DELTA_ARGS(d), merged, chunks, n_segs, P, grad_w)
-  if (d.kind == DELTA_I8) {
-    if (g_is_bf16) GRADW_GO(true, DELTA_I8, true);
-    else GRADW_GO(false, DELTA_I8, true);
-  } else if ((int64_t(n_models) * P) % 2 == 0) {   // see delta_at
-    if (g_is_bf16) GRADW_GO(true, DELTA_BF16, true);
-    else GRADW_GO(false, DELTA_BF16, true);
-  } else {
-    if (g_is_bf16) GRADW_GO(true, DELTA_BF16, false);
-    else GRADW_GO(false, DELTA_BF16, false);
-  }
-#undef GRADW_GO
-}
-
-void launch_axpy_packed(float* w, const PackedView& d, int row, float alpha,
-                        int64_t P, hipStream_t s) {
-  const int block = 256;
-  const bool v4 = packed_vec4(d, P);
-  const int grid = elementwise_grid(P, block, v4 ? 4 : 1);
-  if (d.kind == DELTA_I8)
-    axpy_packed_k<DELTA_I8, 4><<<grid, block, 0, s>>>(
-        w, DELTA_ARGS(d), row, alpha, P);
-  else if (v4)
-    axpy_packed_k<DELTA_BF16, 4><<<grid, block, 0, s>>>(
-        w, DELTA_ARGS(d), row, alpha, P);
-  else
-    axpy_packed_k<DELTA_BF16, 1><<<grid, block, 0, s>>>(
-        w, DELTA_ARGS(d), row, alpha, P);
-}
-
 void launch_delta_quantize_int8(const float* w, const float* base, int64_t P,
                                 int block, int64_t nb, signed char* codes,
                                 float* scales, hipStream_t s) {
@@ -1122,20 +1128,6 @@ void launch_delta_quantize_int8(const float* w, const float* base, int64_t P,
   if (threads < 64) threads = 64;
   delta_quantize_int8_k<<<unsigned(nb), threads, 0, s>>>(w, base, P, block,
                                                          codes, scales);
-}
-
-// ---- top-k deltas -------------------------------------------------------------
-namespace {
-TopkArgs topk_args(const TopkView& d) {
-  const int block = 1 << d.shift;
-  return TopkArgs{d.data, d.ld, d.shift, d.k,
-                  block < TOPK_TILE ? block : TOPK_TILE};
-}
-}  // namespace
-
-size_t dta_topk_merge_shmem(int n_models, int n_segs, int block) {
-  return 2 * sizeof(float) * size_t(block < TOPK_TILE ? block : TOPK_TILE) +
-         merge_shmem(n_models, n_segs);
 }
 
 void launch_delta_topk(const float* w, const float* base,
@@ -1148,39 +1140,3 @@ void launch_delta_topk(const float* w, const float* base,
       w, base, residual_in, residual_out, P, block, k, entries);
 }
 
-void launch_weighted_merge_topk(const float* base, const TopkView& d,
-                                const float* W, const int64_t* offsets,
-                                int n_models, int n_segs, int64_t P,
-                                float* out, hipStream_t s) {
-  const TopkArgs a = topk_args(d);
-  const int64_t n_tiles = (P + a.tile - 1) / a.tile;
-  const int grid =
-      int(n_tiles < MAX_RESIDENT_BLOCKS ? n_tiles : MAX_RESIDENT_BLOCKS);
-  const size_t shmem = dta_topk_merge_shmem(n_models, n_segs, 1 << d.shift);
-  weighted_merge_topk_k<<<grid, TOPK_THREADS, shmem, s>>>(
-      base, a, W, offsets, n_models, n_segs, P, out);
-}
-
-void launch_grad_merge_weights_topk(const void* g, bool g_is_bf16,
-                                    const float* base, const TopkView& d,
-                                    const float* merged,
-                                    const int64_t* chunks, int n_models,
-                                    int n_chunks, int64_t P, float* grad_w,
-                                    int n_segs, hipStream_t s) {
-  const TopkArgs a = topk_args(d);
-  dim3 grid(n_chunks, n_models);
-  const size_t shmem = 2 * sizeof(float) * size_t(a.tile);
-  if (g_is_bf16)
-    grad_w_topk_k<true><<<grid, GW_THREADS, shmem, s>>>(
-        g, base, a, merged, chunks, n_segs, P, grad_w);
-  else
-    grad_w_topk_k<false><<<grid, GW_THREADS, shmem, s>>>(
-        g, base, a, merged, chunks, n_segs, P, grad_w);
-}
-
-void launch_axpy_topk(float* w, const TopkView& d, int row, float alpha,
-                      int64_t P, hipStream_t s) {
-  const int block = 256;
-  const int grid = elementwise_grid(d.ld, block, 4);
-  axpy_topk_k<<<grid, block, 0, s>>>(w, topk_args(d), row, alpha, P);
-}

@@ -10,6 +10,7 @@ them to); they sum in the fp32 kernel's order and give its bits.
 """
 
 import functools
+import re
 
 import pytest
 import torch
@@ -264,6 +265,128 @@ def test_packed_bindings_reject_bad_arguments():
         m.axpy_packed(out, codes, scales, 256, 2, 1.0)
     with pytest.raises(RuntimeError):
         m.quantize_int8(base, torch.empty(0, device=DEV), 100)
+
+
+# What the merge entries refuse differently by wire form, each by the
+# message of its check. Every case raises before anything is launched.
+R_N, R_P, R_BLOCK, R_K = 2, 4100, 1024, 4
+R_NB = (R_P + R_BLOCK - 1) // R_BLOCK
+
+
+def _off16(t):
+    """A tensor like ``t`` that starts 4 bytes past a 16-byte boundary."""
+    skip = 4 // t.element_size()
+    flat = torch.zeros(t.numel() + 16, dtype=t.dtype, device=t.device)
+    return flat[skip:skip + t.numel()].view(t.shape)
+
+
+def _ones(*shape):
+    return torch.ones(*shape, device=DEV)
+
+
+REFUSALS = [
+    # the packed and top-k entries read 16 B vectors
+    ("merge_packed", "bf16", {"base": _off16}, "base must be 16-byte aligned"),
+    ("merge_packed", "int8", {"out": _off16}, "out must be 16-byte aligned"),
+    ("merge_packed", "topk", {"base": _off16}, "base must be 16-byte aligned"),
+    ("merge_packed", "bf16", {"bf16": _off16},
+     "packed data must be 16-byte aligned"),
+    ("merge_packed", "topk", {"topk": _off16},
+     "topk entries must be 16-byte aligned"),
+    ("grad_w_packed", "int8", {"merged": _off16},
+     "merged must be 16-byte aligned"),
+    ("grad_w_packed", "bf16", {"g": _off16}, "g must be 16-byte aligned"),
+    ("axpy_packed", "int8", {"w": _off16}, "w must be 16-byte aligned"),
+    ("axpy_packed", "topk", {"w": _off16}, "w must be 16-byte aligned"),
+    ("trimmed", "bf16", {"bf16": _off16},
+     "packed data must be 16-byte aligned"),
+    # the fp32 entries ask for no alignment, and top-k grad_W none of g:
+    # they get past it, to a refusal that comes later
+    ("merge_f32", "fp32", {"base": _off16, "out": _off16, "fp32": _off16,
+                           "W": lambda t: _ones(3, 1)},
+     "W must be [n_models, n_segs]"),
+    ("grad_w_f32", "fp32", {"base": _off16, "merged": _off16, "g": _off16,
+                            "fp32": _off16, "offs": lambda t: t - 1},
+     "offsets must run from 0 to P"),
+    ("grad_w_packed", "topk", {"g": _off16, "offs": lambda t: t - 1},
+     "offsets must run from 0 to P"),
+    # forms an entry does not take
+    ("merge_packed", "fp32", {}, "packed data must be bf16 or int8"),
+    ("grad_w_packed", "fp32", {}, "packed data must be bf16 or int8"),
+    ("axpy_packed", "fp32", {}, "packed data must be bf16 or int8"),
+    ("merge_f32", "bf16", {}, "deltas must be fp32"),
+    ("merge_f32", "topk", {}, "deltas must be fp32"),
+    ("grad_w_f32", "int8", {}, "deltas must be fp32"),
+    ("trimmed", "topk", {}, "top-k deltas have no coordinate-wise median"),
+    # shapes, by form
+    ("merge_packed", "bf16", {"bf16": lambda t: t[:, :4096].contiguous()},
+     "bf16 deltas must be [N, P]"),
+    ("merge_packed", "topk", {"block": lambda b: 0},
+     "topk entries must be [N, nb*k]"),
+    ("axpy_packed", "topk", {"topk": lambda t: t.new_zeros(R_N, 24)},
+     "topk entries must be [N, nb*k], nb = ceil(P / block)"),
+    # top-k entries of the right shape that are strided, on the CPU, or of
+    # too many rows
+    ("merge_packed", "topk",
+     {"topk": lambda t: t.new_zeros(R_N, 2 * R_NB * R_K)[:, ::2]},
+     "topk entries must be a contiguous int32 [N, nb*k] GPU tensor"),
+    ("axpy_packed", "topk", {"topk": lambda t: t.cpu()},
+     "topk entries must be a contiguous int32 [N, nb*k] GPU tensor"),
+    ("grad_w_packed", "topk", {"topk": lambda t: t.new_zeros(33, R_NB * R_K)},
+     "topk deltas: 1 <= n_models <="),
+    # 8193 int64 offsets are past the 64 KiB of LDS on their own
+    ("merge_f32", "fp32", {"offs": lambda t: t.new_zeros(8193)},
+     "offsets do not fit the LDS budget"),
+    # 2 x 3600 weights fit the LDS budget next to their offsets (57616 B),
+    # not behind the two 1024-element tiles of the top-k merge (+ 8192 B)
+    ("merge_packed", "topk", {"W": lambda t: _ones(R_N, 3600),
+                              "offs": lambda t: torch.arange(3601,
+                                                             device=DEV)},
+     "topk merge: tiles + offsets + W do not fit"),
+]
+
+
+@pytest.mark.parametrize(
+    "entry,form,changes,message", REFUSALS,
+    ids=[f"{e}-{f}-{'+'.join(c) or 'as_is'}" for e, f, c, _ in REFUSALS])
+def test_merge_entries_refuse_by_form(entry, form, changes, message):
+    m = _ext()
+    a = {
+        "base": torch.zeros(R_P, device=DEV),
+        "out": torch.zeros(R_P, device=DEV),
+        "merged": torch.zeros(R_P, device=DEV),
+        "w": torch.zeros(R_P, device=DEV),
+        "g": torch.zeros(R_P, device=DEV),
+        "W": _ones(R_N, 1),
+        "offs": torch.tensor([0, R_P], device=DEV),
+        "block": R_BLOCK,
+        "fp32": torch.zeros(R_N, R_P, device=DEV),
+        "bf16": torch.zeros(R_N, R_P, dtype=torch.bfloat16, device=DEV),
+        "int8": torch.zeros(R_N, R_NB * R_BLOCK, dtype=torch.int8,
+                            device=DEV),
+        "topk": torch.zeros(R_N, R_NB * R_K, dtype=torch.int32, device=DEV),
+    }
+    for name, change in changes.items():
+        a[name] = change(a[name])
+    data = a[form]
+    scales = _ones(R_N, R_NB) if form == "int8" else torch.empty(0, device=DEV)
+    calls = {
+        "merge_f32": lambda: m.weighted_merge(
+            a["base"], data, a["W"], a["offs"], a["out"]),
+        "merge_packed": lambda: m.weighted_merge_packed(
+            a["base"], data, scales, a["block"], a["W"], a["offs"], a["out"]),
+        "grad_w_f32": lambda: m.grad_merge_weights(
+            a["g"], a["base"], data, a["merged"], a["offs"]),
+        "grad_w_packed": lambda: m.grad_merge_weights_packed(
+            a["g"], a["base"], data, scales, a["block"], a["merged"],
+            a["offs"]),
+        "axpy_packed": lambda: m.axpy_packed(
+            a["w"], data, scales, a["block"], 0, 1.0),
+        "trimmed": lambda: m.robust.trimmed_merge(
+            a["base"], data, scales, a["block"], 0, a["out"], None),
+    }
+    with pytest.raises(RuntimeError, match=re.escape(message)):
+        calls[entry]()
 
 
 # ---------------------------------------------------------------------------
