@@ -83,6 +83,11 @@ def main(argv=None) -> int:
                           "weights as int8 codes + group scales "
                           "(models.quantize_for_serving); changes the "
                           "numbers the model produces")
+    top.add_argument("--serve-kv", choices=["bf16", "int8"], default="bf16",
+                     help="serve: int8 keeps the KV cache as int8 codes + "
+                          "one fp32 scale per (token, KV head) row "
+                          "(ops.kv_quantize); about half the cache bytes, "
+                          "changes the numbers the model produces")
     top.add_argument("--src", default=None,
                      help="convert: HF checkpoint directory "
                           "(save_pretrained layout: config.json + "
@@ -163,7 +168,8 @@ def main(argv=None) -> int:
             print(f"int8 weights: {q['converted']} layers converted, "
                   f"{q['kept']} kept, {q['bytes_before']} -> "
                   f"{q['bytes_after']} bytes")
-        srv = InferenceServer(model, device, port=ns.port)
+        srv = InferenceServer(model, device, port=ns.port,
+                              kv_cache=ns.serve_kv)
         srv.start()
         print(f"inference server on :{srv.port} (POST /generate)")
         try:

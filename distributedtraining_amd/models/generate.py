@@ -90,7 +90,8 @@ def generate(model, input_ids: torch.Tensor, max_new_tokens: int,
              eos_token_id: Optional[int] = None,
              generator: Optional[torch.Generator] = None,
              use_cache: bool = False,
-             seed: Optional[int] = None) -> torch.Tensor:
+             seed: Optional[int] = None,
+             kv_cache: str = "bf16") -> torch.Tensor:
     """Extend ``input_ids`` [B, S] by up to ``max_new_tokens``.
 
     temperature 0 = greedy; top_k > 0 restricts sampling to the k highest
@@ -104,11 +105,18 @@ def generate(model, input_ids: torch.Tensor, max_new_tokens: int,
     and on the GPU cached decode replays decode step, sampler and counter
     tick as one graph with the host looking at ``done`` every 16 tokens.
     Output shape and early stop are those of the default path.
+
+    ``kv_cache`` ("bf16" or "int8", with ``use_cache``): the format of the KV
+    cache (``KVCache(kv_dtype=)``). int8 halves the cache and the decode
+    attention traffic and changes the numbers from the second new token on;
+    prefill attends the freshly computed bf16 K and V either way.
     """
+    if kv_cache not in ("bf16", "int8"):
+        raise ValueError(f"generate: kv_cache {kv_cache!r} (bf16 or int8)")
     if seed is not None:
         return _generate_seeded(model, input_ids, max_new_tokens, temperature,
                                 top_k, top_p, eos_token_id, use_cache,
-                                int(seed))
+                                int(seed), kv_cache)
     model_was_training = model.training
     model.eval()
     n_pos = getattr(model, "cfg").n_positions
@@ -118,7 +126,7 @@ def generate(model, input_ids: torch.Tensor, max_new_tokens: int,
         if use_cache and hasattr(model, "prefill"):
             total = min(ids.shape[1] + max_new_tokens, n_pos)
             cache = model.new_cache(ids.shape[0], total, ids.device,
-                                    graphable=ids.is_cuda)
+                                    graphable=ids.is_cuda, kv_dtype=kv_cache)
             logits = model.prefill(ids, cache).float()
             dec = None
             for _ in range(max_new_tokens):
@@ -165,7 +173,7 @@ _POLL = 16     # tokens between two host looks at ``done`` (seeded path)
 
 
 def _generate_seeded(model, input_ids, max_new_tokens, temperature, top_k,
-                     top_p, eos, use_cache, seed):
+                     top_p, eos, use_cache, seed, kv_cache="bf16"):
     from .. import ops
     from ..ops.backend import require_ext
     model_was_training = model.training
@@ -201,7 +209,8 @@ def _generate_seeded(model, input_ids, max_new_tokens, temperature, top_k,
         n_new = min(max_new_tokens, total - S + 1)
         if n_new <= 0:
             return input_ids
-        cache = model.new_cache(B, total, dev, graphable=input_ids.is_cuda)
+        cache = model.new_cache(B, total, dev, graphable=input_ids.is_cuda,
+                                kv_dtype=kv_cache)
         ids = torch.zeros(B, S + n_new, dtype=torch.long, device=dev)
         ids[:, :S] = input_ids
         tok = torch.zeros(B, 1, dtype=torch.long, device=dev)

@@ -233,13 +233,34 @@ class KVCache:
 
     ``split_kv``: the decode-attention route of this cache's decode steps
     (``ops.decode_attention``: 0 one block per head, n >= 1 the split-KV
-    route with n splits, None the measured rule)."""
+    route with n splits, None the measured rule).
+
+    ``kv_dtype="int8"``: ``k`` / ``v`` hold int8 codes and ``k_scale`` /
+    ``v_scale`` one fp32 scale per (token, KV head) row ([B, H, Lp],
+    ``ops.kv_quantize`` format, docs/serving.md): about half the bytes and
+    the decode-attention traffic, different numbers. ``n_head`` (query
+    heads, default the KV heads) lets a GPU cache check the int8 decode
+    kernel's shape contract at construction."""
 
     def __init__(self, n_layer: int, batch: int, n_kv_head: int,
                  max_len: int, head_dim: int, device, dtype=None,
-                 graphable: bool = False, split_kv: Optional[int] = None):
+                 graphable: bool = False, split_kv: Optional[int] = None,
+                 kv_dtype: str = "bf16", n_head: Optional[int] = None):
+        if kv_dtype not in ("bf16", "int8"):
+            raise ValueError(f"KVCache: kv_dtype {kv_dtype!r} (bf16 or int8)")
         dtype = dtype or torch.bfloat16
         self.split_kv = split_kv
+        self.kv_dtype = kv_dtype
+        self.k_scale = self.v_scale = None
+        if kv_dtype == "int8":
+            if torch.device(device).type == "cuda":
+                ops._kv_q8_contract(n_head or n_kv_head, n_kv_head, head_dim)
+            dtype = torch.int8
+            lp = ops.kv_scale_len(max_len)
+            self.k_scale = [torch.ones(batch, n_kv_head, lp, device=device)
+                            for _ in range(n_layer)]
+            self.v_scale = [torch.ones_like(self.k_scale[0])
+                            for _ in range(n_layer)]
         self.k = [torch.zeros(batch, n_kv_head, max_len, head_dim,
                               device=device, dtype=dtype)
                   for _ in range(n_layer)]
@@ -258,6 +279,13 @@ class KVCache:
         if self.len + S > self.max_len:
             raise ValueError(
                 f"KV cache overflow: {self.len}+{S} > {self.max_len}")
+        if self.kv_dtype == "int8":
+            ops.kv_append_q8(
+                k_new, v_new, self.k[layer], self.k_scale[layer],
+                self.v[layer], self.v_scale[layer],
+                self.pos_dev if self.pos_dev is not None and S == 1
+                and k_new.is_cuda else self.len)
+            return
         if self.pos_dev is not None and S == 1 and k_new.is_cuda:
             from ..ops.backend import require_ext
             B = k_new.shape[0]
@@ -270,6 +298,17 @@ class KVCache:
             k_new.transpose(1, 2))
         self.v[layer][:, :, self.len:self.len + S].copy_(
             v_new.transpose(1, 2))
+
+    def scales(self, layer: int) -> dict:
+        """``k_scale`` / ``v_scale`` keywords of ``ops.decode_attention``."""
+        if self.kv_dtype != "int8":
+            return {}
+        return {"k_scale": self.k_scale[layer], "v_scale": self.v_scale[layer]}
+
+    def nbytes(self) -> int:
+        """Bytes of the cache tensors (codes and scales)."""
+        ts = self.k + self.v + (self.k_scale or []) + (self.v_scale or [])
+        return sum(t.numel() * t.element_size() for t in ts)
 
     def advance(self, n: int) -> None:
         self.len += n
@@ -296,7 +335,7 @@ def _gpt2_block_attn_cached(blk: GPT2Block, x: torch.Tensor,
         o = ops.decode_attention(q.reshape(B, H, D), cache.k[i],
                                  cache.v[i], cache.len + 1,
                                  kv_len_dev=cache.pos_dev,
-                                 split_kv=cache.split_kv)
+                                 split_kv=cache.split_kv, **cache.scales(i))
         o = o.view(B, 1, E)
     else:
         assert cache.len == 0, "prefill must start an empty cache"
@@ -332,12 +371,14 @@ def _gpt2_cached_forward(model: "GPT2LM", input_ids: torch.Tensor,
 
 def _gpt2_new_cache(self: "GPT2LM", batch: int, max_len: int, device,
                     dtype=None, graphable: bool = False,
-                    split_kv: Optional[int] = None) -> KVCache:
+                    split_kv: Optional[int] = None,
+                    kv_dtype: str = "bf16") -> KVCache:
     cfg = self.cfg
     return KVCache(cfg.n_layer, batch, cfg.n_head, max_len,
                    cfg.n_embd // cfg.n_head, device,
                    dtype or next(self.parameters()).dtype,
-                   graphable=graphable, split_kv=split_kv)
+                   graphable=graphable, split_kv=split_kv,
+                   kv_dtype=kv_dtype, n_head=cfg.n_head)
 
 
 def _gpt2_prefill(self: "GPT2LM", input_ids: torch.Tensor,

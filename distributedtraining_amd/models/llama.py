@@ -222,7 +222,7 @@ def _llama_block_attn_cached(blk: LlamaBlock, x: torch.Tensor, cos, sin,
         o = ops.decode_attention(q.reshape(B, blk.n_head, D), cache.k[i],
                                  cache.v[i], cache.len + 1,
                                  kv_len_dev=cache.pos_dev,
-                                 split_kv=cache.split_kv)
+                                 split_kv=cache.split_kv, **cache.scales(i))
         o = o.view(B, 1, E)
     else:
         assert cache.len == 0, "prefill must start an empty cache"
@@ -253,13 +253,15 @@ def _llama_cached_forward(model: "LlamaLM", input_ids: torch.Tensor,
 
 
 def _llama_new_cache(self: "LlamaLM", batch: int, max_len: int, device,
-                     dtype=None, graphable: bool = False, split_kv=None):
+                     dtype=None, graphable: bool = False, split_kv=None,
+                     kv_dtype: str = "bf16"):
     from .gpt2 import KVCache
     cfg = self.cfg
     return KVCache(cfg.n_layer, batch, cfg.n_kv_head or cfg.n_head,
                    max_len, cfg.n_embd // cfg.n_head, device,
                    dtype or next(self.parameters()).dtype,
-                   graphable=graphable, split_kv=split_kv)
+                   graphable=graphable, split_kv=split_kv,
+                   kv_dtype=kv_dtype, n_head=cfg.n_head)
 
 
 def _llama_prefill(self: "LlamaLM", input_ids: torch.Tensor, cache):

@@ -46,7 +46,9 @@ __all__ = [
     "add_rms_norm",
     "cross_entropy_loss", "lm_head_ce", "lm_head_loss",
     "embedding_fwd", "check_q_lo", "check_doc_start", "q_lo_inverse",
-    "decode_attention", "decode_split_plan", "rope", "adamw_step", "delta_sub", "axpy_",
+    "decode_attention", "decode_split_plan", "decode_split_plan_q8",
+    "kv_quantize", "kv_dequantize",
+    "kv_append_q8", "kv_scale_len", "rope", "adamw_step", "delta_sub", "axpy_",
     "weighted_merge", "trimmed_merge", "median_trim",
     "grad_merge_weights", "has_nan", "l2norm",
     "grad_sumsq_blocks", "grad_sumsq_partials", "step_control",
@@ -955,6 +957,21 @@ def decode_split_plan(B: int, H: int, Hk: int, Lmax: int, D: int,
     return max(1, min(-(-cus // (B * Hk)), Lmax // 512))
 
 
+def decode_split_plan_q8(B: int, H: int, Hk: int, Lmax: int, D: int,
+                         cus: int = 256) -> int:
+    """Split count of the int8-cache decode route (always >= 1: it has no
+    one-block-per-head form). Its own rule, from profiles/r17_kv_int8.md
+    (tools/kv_q8_ab.py, MI355X): at ``decode_split_plan``'s count the int8
+    route was 11 % to 33 % behind its best arm where B * Hk is 64 or 128
+    (Llama-3-8B and Qwen2-7B heads at batch 16), because a block streams
+    half the bytes and one block per CU no longer covers the latency. Two
+    blocks per CU, still in splits of at least 512 keys:
+    clamp(ceil(2 CUs / (B Hk)), 1, Lmax / 512), a measured arm within 6 % of
+    the best arm at every shape of that table."""
+    _kv_q8_contract(H, Hk, D)
+    return max(1, min(-(-2 * cus // (B * Hk)), Lmax // 512))
+
+
 def _decode_split_candidate(B: int, Hk: int, Lmax: int, cus: int = 256) -> int:
     """clamp(ceil(2 CUs / (B Hk)), 1, Lmax / 256), the count
     tools/decode_attn_ab.py centres its sweep on (two resident blocks per
@@ -962,11 +979,67 @@ def _decode_split_candidate(B: int, Hk: int, Lmax: int, cus: int = 256) -> int:
     return max(1, min(-(-2 * cus // (B * Hk)), Lmax // 256))
 
 
+def kv_scale_len(max_len: int) -> int:
+    """Length of an int8 KV cache's scale rows for a capacity of ``max_len``
+    keys: rounded up to the 32-key tile whose scales the decode kernel loads
+    as 16 B vectors (hip/attention.hip, attn_decode_split_q8_k)."""
+    return (max_len + 31) // 32 * 32
+
+
+def kv_quantize(x: torch.Tensor):
+    """The int8 KV-cache format: ``x [..., D]`` (bf16 / fp32) -> (codes int8
+    ``[..., D]``, scale fp32 ``[...]``), one group per last-dim row, the
+    scale rule of ``quantize_weight_int8``: scale = amax|row| / 127 (1.0 for
+    a zero row), code = clamp(rint(row / scale), -127, 127) in fp32 with
+    round-half-even. The represented value is ``float(code) * scale``."""
+    xf = x.detach().to(torch.float32)
+    amax = xf.abs().amax(dim=-1)
+    # tensor / tensor: a true fp32 divide on every device (a GPU divide by a
+    # Python scalar multiplies by its rounded reciprocal)
+    scale = amax / torch.full_like(amax, 127.0)
+    scale = torch.where(scale == 0, torch.ones_like(scale), scale)
+    q = torch.clamp(torch.round(xf / scale[..., None]), -127, 127)
+    return q.to(torch.int8), scale
+
+
+def kv_dequantize(codes: torch.Tensor, scale: torch.Tensor,
+                  dtype: torch.dtype = torch.bfloat16) -> torch.Tensor:
+    """``float(code) * scale`` rounded once to ``dtype``."""
+    return (codes.to(torch.float32) * scale[..., None]).to(dtype)
+
+
+def kv_append_q8(k_new: torch.Tensor, v_new: torch.Tensor,
+                 k_codes: torch.Tensor, k_scale: torch.Tensor,
+                 v_codes: torch.Tensor, v_scale: torch.Tensor, pos) -> None:
+    """Quantising append into an int8 KV cache: ``k_new`` / ``v_new``
+    [B, S, Hk, D] (bf16 views, D contiguous) go through ``kv_quantize`` into
+    rows pos .. pos + S - 1 of the code caches [B, Hk, Lmax, D] and the scale
+    rows [B, Hk, Lp]. ``pos``: an int, or the cache's int32 device counter
+    (graph-replayable; GPU). One kernel on the GPU for any S."""
+    S = k_new.shape[1]
+    if use_hip(k_codes):
+        dev_pos = isinstance(pos, torch.Tensor)
+        require_ext().kv_q8.append(
+            k_new, v_new, k_codes, v_codes, k_scale, v_scale,
+            pos if dev_pos else torch.empty(0, dtype=torch.int32,
+                                            device=k_codes.device),
+            0 if dev_pos else int(pos))
+        return
+    pos = int(pos)
+    for new, codes, scale in ((k_new, k_codes, k_scale),
+                              (v_new, v_codes, v_scale)):
+        q, s = kv_quantize(new.transpose(1, 2))          # [B, Hk, S, D]
+        codes[:, :, pos:pos + S] = q
+        scale[:, :, pos:pos + S] = s
+
+
 def decode_attention(q: torch.Tensor, k_cache: torch.Tensor,
                      v_cache: torch.Tensor, kv_len: int,
                      scale: Optional[float] = None,
                      kv_len_dev: Optional[torch.Tensor] = None,
-                     split_kv: Optional[int] = None
+                     split_kv: Optional[int] = None,
+                     k_scale: Optional[torch.Tensor] = None,
+                     v_scale: Optional[torch.Tensor] = None
                      ) -> torch.Tensor:
     """Serving decode step: one new query per head attends the whole KV
     cache. q [B,H,D]; caches [B,Hk,Lmax,D] with the first kv_len rows
@@ -975,18 +1048,37 @@ def decode_attention(q: torch.Tensor, k_cache: torch.Tensor,
     the step hipGraph-replayable. ``split_kv`` (GPU only): 0 the
     one-block-per-head kernel, n >= 1 the split-KV MFMA route with n splits
     of the cache (one block per KV head and split, K/V read once per KV
-    head), None asks ``decode_split_plan``. Inference-only (no autograd)."""
+    head), None asks ``decode_split_plan``. ``k_scale`` / ``v_scale``
+    (fp32 [B,Hk,Lp]): the caches are int8 codes in the ``kv_quantize``
+    format; on the GPU that is the int8 split route, which exists for head
+    groups <= 16 and head dims 64 / 128 only and has no one-block-per-head
+    form (``split_kv=0`` raises; None asks ``decode_split_plan_q8``).
+    Inference-only (no autograd)."""
     if scale is None:
         scale = 1.0 / math.sqrt(q.shape[-1])
+    q8 = k_scale is not None or v_scale is not None
+    if q8:
+        if k_scale is None or v_scale is None:
+            raise ValueError("decode_attention: k_scale and v_scale go together")
+        if k_cache.dtype != torch.int8 or v_cache.dtype != torch.int8:
+            raise ValueError("decode_attention: scales need int8 caches")
     if use_hip(q):
         if split_kv is None:
-            split_kv = decode_split_plan(q.shape[0], q.shape[1],
-                                         k_cache.shape[1], k_cache.shape[2],
-                                         q.shape[2])
+            plan = decode_split_plan_q8 if q8 else decode_split_plan
+            split_kv = plan(q.shape[0], q.shape[1], k_cache.shape[1],
+                            k_cache.shape[2], q.shape[2])
         if split_kv < 0:
             raise ValueError(f"decode_attention: split_kv {split_kv}")
         len_dev = (kv_len_dev if kv_len_dev is not None
                    else torch.empty(0, dtype=torch.int32, device=q.device))
+        if q8:
+            _kv_q8_contract(q.shape[1], k_cache.shape[1], q.shape[2])
+            if split_kv == 0:
+                raise ValueError("decode_attention: the int8 cache has no "
+                                 "one-block-per-head route (split_kv=0)")
+            return require_ext().kv_q8.attn(
+                q.contiguous(), k_cache, v_cache, k_scale, v_scale, kv_len,
+                scale, len_dev, split_kv)
         if split_kv:
             return require_ext().decode_split.attn(
                 q.contiguous(), k_cache, v_cache, kv_len, scale, len_dev,
@@ -1000,12 +1092,25 @@ def decode_attention(q: torch.Tensor, k_cache: torch.Tensor,
     H = q.shape[1]
     kf = k_cache[:, :, :kv_len].float()
     vf = v_cache[:, :, :kv_len].float()
+    if q8:
+        kf = kf * k_scale[:, :, :kv_len, None]
+        vf = vf * v_scale[:, :, :kv_len, None]
     if H != Hk:
         rep = H // Hk
         kf = kf.repeat_interleave(rep, dim=1)
         vf = vf.repeat_interleave(rep, dim=1)
     att = torch.softmax((qf @ kf.transpose(-1, -2)) * scale, dim=-1)
     return (att @ vf).squeeze(2).to(q.dtype)
+
+
+def _kv_q8_contract(H: int, Hk: int, D: int) -> None:
+    """The shapes the int8 decode kernel serves; anything else is an error,
+    never another route."""
+    grp = H // Hk if Hk > 0 and H % Hk == 0 else 0
+    if not 1 <= grp <= 16 or D not in (64, 128):
+        raise ValueError(
+            f"int8 KV cache: needs 1 <= heads per KV head <= 16 and head dim "
+            f"64 / 128, got H = {H}, Hk = {Hk}, D = {D}")
 
 
 # --------------------------------------------------------------------------

@@ -34,7 +34,9 @@
 //   * Serving decode has two routes: attn_decode_k (one block per query
 //     head, fp32 FMAs) and attn_decode_split_k + attn_decode_combine_k (one
 //     block per KV head and cache split, the head group on MFMA); see the
-//     comments at the kernels and ops.decode_split_plan.
+//     comments at the kernels and ops.decode_split_plan. The split route
+//     has an int8-cache sibling, attn_decode_split_q8_k (codes + per-row
+//     scales, written by kv_append_q8_k in embedding.hip).
 //   * swapped QK^T: mfma(A=K_tile, B=Q^T) puts a query's scores in lanes
 //     sharing (lane&15) so the softmax row-reduce is two shfl_xor ops;
 //     exp via the single-instruction exp2 path.
@@ -1282,6 +1284,79 @@ DEV void dec_load_v(s16x8 (&vr)[DTILES], const ushort* vp, int kv0, int end,
                       8 * (g + 4 * (it >> 1)));
 }
 
+// A split with no valid key: o = 0 when it is the only split, else m = -inf
+// (attn_decode_combine_k skips the row). bh0: b * H + first head of the group.
+template <int D>
+DEV void dec_split_empty(ushort* o, float* ws, int64_t bh0, int grp, int split,
+                         int nsplit, int tid) {
+  if (tid >= grp) return;
+  if (nsplit == 1) {
+    for (int c = 0; c < D; ++c) o[(bh0 + tid) * D + c] = 0;
+  } else {
+    float* row = ws + ((bh0 + tid) * nsplit + split) * dta_decode_split_row(D);
+    *reinterpret_cast<f32x4*>(row + D) = f32x4{-INFINITY, 0.f, 0.f, 0.f};
+  }
+}
+
+// Tail of a split block: the 4 wave partials (m, l of query n = lane & 15,
+// acc[t][r] = column 16t + 4g + r) merged in wave order through LDS, then o
+// (nsplit == 1) or the split's workspace row. smem: >= DEC_COMB(D) floats.
+constexpr int DEC_COMB(int D) { return 128 + 4 * 16 * D; }  // m, l [4][16], acc
+template <int DTILES>
+DEV void dec_split_merge(char* smem, const f32x4 (&acc)[DTILES], float m_run,
+                         float l_run, ushort* o, float* ws, int64_t bh0,
+                         int grp, int split, int nsplit) {
+  constexpr int D = 16 * DTILES;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int n = lane & 15, g = lane >> 4;
+  // merge of the 4 wave partials, 16 columns wide; the V tiles are dead
+  __syncthreads();
+  float* cm = reinterpret_cast<float*>(smem);   // [4][16]
+  float* cl = cm + 64;                          // [4][16]
+  float* ca = cl + 64;                          // [4][16][D]
+  if (g == 0) {
+    cm[wid * 16 + n] = m_run;
+    cl[wid * 16 + n] = l_run;
+  }
+#pragma unroll
+  for (int t = 0; t < DTILES; ++t)
+    *reinterpret_cast<f32x4*>(ca + (wid * 16 + n) * D + 16 * t + 4 * g) =
+        acc[t];
+  __syncthreads();
+  for (int u = tid; u < 4 * D; u += 256) {   // (head, 4 columns) units
+    const int hn = u / (D / 4), d4 = (u % (D / 4)) * 4;
+    if (hn >= grp) continue;
+    float mg = -INFINITY;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) mg = fmaxf(mg, cm[w * 16 + hn]);
+    float lg = 0.f;
+    f32x4 s = {0, 0, 0, 0};
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+      const float mw = cm[w * 16 + hn];
+      const float r = (mw == -INFINITY) ? 0.f : __builtin_exp2f(mw - mg);
+      lg += cl[w * 16 + hn] * r;
+      const f32x4 a =
+          *reinterpret_cast<const f32x4*>(ca + (w * 16 + hn) * D + d4);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) s[e] = fmaf(a[e], r, s[e]);
+    }
+    const int64_t bh = bh0 + hn;
+    if (nsplit == 1) {
+      const float inv = lg > 0.f ? 1.0f / lg : 0.f;
+      s16x4 ob;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) ob[e] = short(f2bf(s[e] * inv));
+      *reinterpret_cast<s16x4*>(o + bh * D + d4) = ob;
+    } else {
+      float* row = ws + (bh * nsplit + split) * dta_decode_split_row(D);
+      *reinterpret_cast<f32x4*>(row + d4) = s;
+      if (d4 == 0) *reinterpret_cast<f32x4*>(row + D) = f32x4{mg, lg, 0.f, 0.f};
+    }
+  }
+}
+
 template <int DTILES>  // D = 16*DTILES
 __global__ __launch_bounds__(256)
 __attribute__((target("no-packed-fp32-ops")))
@@ -1296,7 +1371,7 @@ void attn_decode_split_k(const ushort* __restrict__ q,   // [B,H,D]
   constexpr int D = 16 * DTILES;
   constexpr int KS = DTILES / 2;            // 32-column steps of a K row
   constexpr int VT = D * DEC_VP;            // ushorts of one wave's V^T tile
-  constexpr int COMB = 128 + 4 * 16 * D;    // floats: m[4][16] l[4][16] acc
+  constexpr int COMB = DEC_COMB(D);         // floats of the merge
   constexpr int SMEM = 4 * VT * 2 > COMB * 4 ? 4 * VT * 2 : COMB * 4;
   __shared__ __attribute__((aligned(16))) char smem[SMEM];
 
@@ -1312,15 +1387,7 @@ void attn_decode_split_k(const ushort* __restrict__ q,   // [B,H,D]
   const int h0 = hk * grp;
 
   if (start >= end) {   // block-uniform: nothing of this split is valid yet
-    if (tid < grp) {
-      if (nsplit == 1) {
-        for (int c = 0; c < D; ++c) o[(int64_t(b) * H + h0 + tid) * D + c] = 0;
-      } else {
-        float* row = ws + ((int64_t(b) * H + h0 + tid) * nsplit + split) *
-                              dta_decode_split_row(D);
-        *reinterpret_cast<f32x4*>(row + D) = f32x4{-INFINITY, 0.f, 0.f, 0.f};
-      }
-    }
+    dec_split_empty<D>(o, ws, int64_t(b) * H + h0, grp, split, nsplit, tid);
     return;
   }
 
@@ -1418,51 +1485,252 @@ void attn_decode_split_k(const ushort* __restrict__ q,   // [B,H,D]
     }
   }
 
-  // merge of the 4 wave partials, 16 columns wide; the V tiles are dead
-  __syncthreads();
-  float* cm = reinterpret_cast<float*>(smem);   // [4][16]
-  float* cl = cm + 64;                          // [4][16]
-  float* ca = cl + 64;                          // [4][16][D]
-  if (g == 0) {
-    cm[wid * 16 + n] = m_run;
-    cl[wid * 16 + n] = l_run;
+  dec_split_merge<DTILES>(smem, acc, m_run, l_run, o, ws,
+                          int64_t(b) * H + h0, grp, split, nsplit);
+}
+
+// ---------------- decode, split-KV route on an int8 KV cache ---------------
+// The int8 sibling of attn_decode_split_k (format: docs/serving.md): caches
+// are int8 codes [B,Hk,Lmax,D] with one fp32 scale per (token, KV head) row in
+// [B,Hk,Lp], value = float(code) * scale. Same decomposition (one block per
+// split, KV head and batch row, 4 waves on interleaved 32-key tiles, the head
+// group as the 16 MFMA columns), the same wave merge and workspace rows, so
+// attn_decode_combine_k finishes it. The cache bytes per key drop from 4 D to
+// 2 D + 8. How the codes move is this kernel's own:
+//   * No code is ever multiplied by its scale. A code is an integer of
+//     |q| <= 127, exact in bf16, so the MFMAs run on the converted codes and
+//     the per-key scales are applied where a key is a C-layout row (K) or the
+//     contraction index (V).
+//   * K: lane (n, g) loads 16 B = 16 codes of key row n at column 64 s + 16 g
+//     (D/64 loads per row: half the bf16 kernel's). Codes 8 j .. 8 j + 7 are
+//     the A-fragment of MFMA (s, j), as in w8_gemv.hip: contraction slot
+//     8 g + e of that MFMA stands for column 64 s + 16 g + 8 j + e, and the
+//     Q^T B-fragments qb[s][j] are loaded once per block in that order. The
+//     raw score of key 4 g + r (p0) and 16 + 4 g + r (p1) is multiplied by
+//     k_scale[key] * scale * log2e before the mask and the max; the lane
+//     loads its 2 x 4 K scales as two 16 B vectors.
+//   * V: lane (kq, c) = (lane >> 3, lane & 7) loads D/8 bytes of the 4 key
+//     rows 4 kq .. 4 kq + 3 at column c D/8, transposes each 4 x 4 byte block
+//     in registers (v_perm_b32) and writes dwords of 4 keys x 1 column into
+//     the wave's transposed CODE tile [D][DQ8_VP bytes]. The codes convert
+//     to bf16 on the FRAGMENT READ (two 4 B LDS reads -> one A-fragment),
+//     not on the staging write: a lane converts 32 D / 64 codes either way
+//     (every tile element belongs to one lane on both sides), but a byte
+//     tile halves the LDS footprint and the LDS read traffic, and the
+//     staging writes stay whole dwords.
+//   * The per-key V scale is folded into P: pb = bf16(p * v_scale[key]) with
+//     the key the contraction index of P.V, so acc needs no rescale beyond
+//     alpha. l sums the unscaled, unrounded fp32 p.
+//   * Loads run one tile ahead in registers (K codes and the 4 scale vectors
+//     after the score MFMAs, V codes after the staging write). Rows are
+//     clamped into the split and the scale vectors to the split's last tile,
+//     so nothing branches around a load; every branch is block- or
+//     wave-uniform. Masked keys select 0 / -inf, never multiply, so the
+//     scales past kvlen may hold anything.
+//   * Scale padding: a scale vector load covers keys 32 i + 4 g .. + 3 of a
+//     tile that holds at least one valid key, i.e. indices below
+//     ceil32(Lmax). Hence Lp >= dta_kv_q8_scale_len(Lmax) = Lmax rounded up
+//     to a multiple of 32, and Lp % 4 == 0 keeps every row 16 B aligned.
+// Rounding points: p * v_scale is rounded to bf16 once; scores, p, l, alpha,
+// the accumulators and all partials are fp32; o is rounded once.
+typedef __attribute__((ext_vector_type(4))) int i32x4;
+template <int N> using i32xN = int __attribute__((ext_vector_type(N)));
+constexpr int DQ8_VP = 36;   // bytes per V^T code row: 32 keys + 4 (9 dwords)
+
+template <int DTILES>
+DEV void dq8_load_k(i32x4 (&ka)[DTILES / 4], i32x4 (&kb)[DTILES / 4],
+                    const char* kp, int kv0, int end, int lane) {
+  constexpr int D = 16 * DTILES;
+  const int n = lane & 15, g = lane >> 4;
+  const int ra = min(kv0 + n, end - 1), rb = min(kv0 + 16 + n, end - 1);
+#pragma unroll
+  for (int s = 0; s < DTILES / 4; ++s) {
+    ka[s] = *reinterpret_cast<const i32x4*>(kp + int64_t(ra) * D + 64 * s +
+                                            16 * g);
+    kb[s] = *reinterpret_cast<const i32x4*>(kp + int64_t(rb) * D + 64 * s +
+                                            16 * g);
   }
+}
+// sc[0], sc[1]: K scales of keys 4g + r and 16 + 4g + r of the tile at kv0;
+// sc[2], sc[3]: the V scales. Past the split: its last tile again.
+DEV void dq8_load_scales(f32x4 (&sc)[4], const float* ksp, const float* vsp,
+                         int kv0, int end, int g) {
+  const int tb = (kv0 < end ? kv0 : ((end - 1) & ~31)) + 4 * g;
+  sc[0] = *reinterpret_cast<const f32x4*>(ksp + tb);
+  sc[1] = *reinterpret_cast<const f32x4*>(ksp + tb + 16);
+  sc[2] = *reinterpret_cast<const f32x4*>(vsp + tb);
+  sc[3] = *reinterpret_cast<const f32x4*>(vsp + tb + 16);
+}
+// vr[i]: D/8 bytes of key row kv0 + 4 kq + i at column c D/8
+template <int DTILES>
+DEV void dq8_load_v(i32xN<DTILES / 2> (&vr)[4], const char* vp, int kv0,
+                    int end, int lane) {
+  constexpr int D = 16 * DTILES;
+  const int kq = lane >> 3, c = lane & 7;
 #pragma unroll
-  for (int t = 0; t < DTILES; ++t)
-    *reinterpret_cast<f32x4*>(ca + (wid * 16 + n) * D + 16 * t + 4 * g) =
-        acc[t];
-  __syncthreads();
-  for (int u = tid; u < 4 * D; u += 256) {   // (head, 4 columns) units
-    const int hn = u / (D / 4), d4 = (u % (D / 4)) * 4;
-    if (hn >= grp) continue;
-    float mg = -INFINITY;
+  for (int i = 0; i < 4; ++i)
+    vr[i] = *reinterpret_cast<const i32xN<DTILES / 2>*>(
+        vp + int64_t(min(kv0 + 4 * kq + i, end - 1)) * D + c * (D / 8));
+}
+
+template <int DTILES>  // D = 16*DTILES
+__global__ __launch_bounds__(256)
+__attribute__((target("no-packed-fp32-ops")))
+void attn_decode_split_q8_k(const ushort* __restrict__ q,   // [B,H,D]
+                            const char* __restrict__ kc,    // [B,Hk,Lmax,D]
+                            const char* __restrict__ vc,
+                            const float* __restrict__ ksc,  // [B,Hk,Lp]
+                            const float* __restrict__ vsc,
+                            ushort* __restrict__ o,         // [B,H,D]
+                            float* __restrict__ ws,  // [B,H,nsplit,D+4]
+                            int H, int grp, int Lmax, int Lp, int kvlen,
+                            const int* __restrict__ len_p, int chunk,
+                            float scale) {
+  constexpr int D = 16 * DTILES;
+  constexpr int KS = DTILES / 4;            // 64-column steps of a K row
+  constexpr int VW = DTILES / 2;            // dwords of a lane's V row piece
+  constexpr int VT = D * DQ8_VP;            // bytes of one wave's V^T tile
+  constexpr int COMB = DEC_COMB(D);         // floats of the merge
+  constexpr int SMEM = 4 * VT > COMB * 4 ? 4 * VT : COMB * 4;
+  __shared__ __attribute__((aligned(16))) char smem[SMEM];
+
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int n = lane & 15, g = lane >> 4;
+  const int split = blockIdx.x, nsplit = gridDim.x;
+  const int hk = blockIdx.y, Hk = gridDim.y, b = blockIdx.z;
+  if (len_p) kvlen = *len_p + 1;
+  kvlen = min(kvlen, Lmax);
+  const int start = split * chunk;
+  const int end = min(kvlen, start + chunk);
+  const int h0 = hk * grp;
+
+  if (start >= end) {   // block-uniform: nothing of this split is valid yet
+    dec_split_empty<D>(o, ws, int64_t(b) * H + h0, grp, split, nsplit, tid);
+    return;
+  }
+
+  const int64_t bhk = int64_t(b) * Hk + hk;
+  const char* kp = kc + bhk * Lmax * D;
+  const char* vp = vc + bhk * Lmax * D;
+  const float* ksp = ksc + bhk * Lp;
+  const float* vsp = vsc + bhk * Lp;
+  const float sc2 = scale * LOG2E;
+
+  // Q^T B-fragments: qb[s][j] of lane (n, g) = q[h0 + n][64s + 16g + 8j ..]
+  bf16x8 qb[KS][2];
+  {
+    const ushort* qp = q + (int64_t(b) * H + h0 + min(n, grp - 1)) * D;
 #pragma unroll
-    for (int w = 0; w < 4; ++w) mg = fmaxf(mg, cm[w * 16 + hn]);
-    float lg = 0.f;
-    f32x4 s = {0, 0, 0, 0};
+    for (int s = 0; s < KS; ++s)
 #pragma unroll
-    for (int w = 0; w < 4; ++w) {
-      const float mw = cm[w * 16 + hn];
-      const float r = (mw == -INFINITY) ? 0.f : __builtin_exp2f(mw - mg);
-      lg += cl[w * 16 + hn] * r;
-      const f32x4 a =
-          *reinterpret_cast<const f32x4*>(ca + (w * 16 + hn) * D + d4);
+      for (int j = 0; j < 2; ++j) {
+        s16x8 v =
+            *reinterpret_cast<const s16x8*>(qp + 64 * s + 16 * g + 8 * j);
+        if (n >= grp) v = s16x8{0, 0, 0, 0, 0, 0, 0, 0};
+        qb[s][j] = as_bf16x8(v);
+      }
+  }
+
+  f32x4 acc[DTILES];
 #pragma unroll
-      for (int e = 0; e < 4; ++e) s[e] = fmaf(a[e], r, s[e]);
+  for (int t = 0; t < DTILES; ++t) acc[t] = f32x4{0, 0, 0, 0};
+  float m_run = -INFINITY, l_run = 0.f;   // of query n, in exp2 units
+
+  char* vt = smem + wid * VT;
+  const int kq = lane >> 3, vcol = (lane & 7) * (D / 8);
+  i32x4 ka[KS], kb[KS];     // codes of key rows kv0 + n and kv0 + 16 + n
+  f32x4 sc[4];              // K and V scales of the lane's 8 keys
+  i32xN<VW> vr[4];
+  // wave wid owns tiles wid, wid + 4, ... of the split (wave-uniform loop)
+  int kv0 = start + 32 * wid;
+  dq8_load_k<DTILES>(ka, kb, kp, kv0, end, lane);   // clamped: in bounds
+  dq8_load_scales(sc, ksp, vsp, kv0, end, g);
+  __builtin_amdgcn_sched_barrier(0);   // K before V, as in the loop
+  dq8_load_v<DTILES>(vr, vp, kv0, end, lane);
+  for (; kv0 < end; kv0 += 128) {
+    f32x4 p0 = {0, 0, 0, 0}, p1 = {0, 0, 0, 0};
+#pragma unroll
+    for (int s = 0; s < KS; ++s)
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        p0 = mfma_bf16(codes_to_bf16(ka[s][2 * j], ka[s][2 * j + 1]),
+                       qb[s][j], p0);
+        p1 = mfma_bf16(codes_to_bf16(kb[s][2 * j], kb[s][2 * j + 1]),
+                       qb[s][j], p1);
+      }
+    const f32x4 ksa = sc[0], ksb = sc[1], vsa = sc[2], vsb = sc[3];
+    // clamped: in bounds even past the last tile
+    dq8_load_k<DTILES>(ka, kb, kp, kv0 + 128, end, lane);
+    dq8_load_scales(sc, ksp, vsp, kv0 + 128, end, g);
+
+    float mx = -INFINITY;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int k0a = kv0 + 4 * g + r;
+      p0[r] = k0a < end ? p0[r] * (ksa[r] * sc2) : -INFINITY;
+      p1[r] = k0a + 16 < end ? p1[r] * (ksb[r] * sc2) : -INFINITY;
+      mx = fmaxf(mx, fmaxf(p0[r], p1[r]));
     }
-    const int64_t bh = int64_t(b) * H + h0 + hn;
-    if (nsplit == 1) {
-      const float inv = lg > 0.f ? 1.0f / lg : 0.f;
-      s16x4 ob;
+    mx = fmaxf(mx, __shfl_xor(mx, 16));
+    mx = fmaxf(mx, __shfl_xor(mx, 32));
+    const float m_new = fmaxf(m_run, mx);   // finite: key kv0 is valid
+    const float alpha =
+        (m_run == -INFINITY) ? 0.f : __builtin_exp2f(m_run - m_new);
+    float pv[8];
+    float psum = 0.f;
 #pragma unroll
-      for (int e = 0; e < 4; ++e) ob[e] = short(f2bf(s[e] * inv));
-      *reinterpret_cast<s16x4*>(o + bh * D + d4) = ob;
-    } else {
-      float* row = ws + (bh * nsplit + split) * dta_decode_split_row(D);
-      *reinterpret_cast<f32x4*>(row + d4) = s;
-      if (d4 == 0) *reinterpret_cast<f32x4*>(row + D) = f32x4{mg, lg, 0.f, 0.f};
+    for (int r = 0; r < 4; ++r) {
+      const bool v0 = p0[r] != -INFINITY, v1 = p1[r] != -INFINITY;
+      const float e0 = v0 ? __builtin_exp2f(p0[r] - m_new) : 0.f;
+      const float e1 = v1 ? __builtin_exp2f(p1[r] - m_new) : 0.f;
+      psum += e0 + e1;
+      pv[r] = v0 ? e0 * vsa[r] : 0.f;
+      pv[4 + r] = v1 ? e1 * vsb[r] : 0.f;
+    }
+    psum += __shfl_xor(psum, 16);
+    psum += __shfl_xor(psum, 32);
+    l_run = l_run * alpha + psum;
+    m_run = m_new;
+    // slot 8g + j of the contraction = key 16*(j >> 2) + 4g + (j & 3)
+    const bf16x8 pb = pack_bf16x8(pv);
+
+    // V(i) codes -> transposed tile; the previous tile's reads are done
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int w = 0; w < VW; ++w) {
+      // 4 keys x 4 columns of bytes -> 4 columns x 4 keys (key 0 lowest)
+      const int a0 = __builtin_amdgcn_perm(vr[1][w], vr[0][w], 0x05010400);
+      const int a1 = __builtin_amdgcn_perm(vr[1][w], vr[0][w], 0x07030602);
+      const int b0 = __builtin_amdgcn_perm(vr[3][w], vr[2][w], 0x05010400);
+      const int b1 = __builtin_amdgcn_perm(vr[3][w], vr[2][w], 0x07030602);
+      char* dst = vt + (vcol + 4 * w) * DQ8_VP + 4 * kq;
+      *reinterpret_cast<int*>(dst) =
+          __builtin_amdgcn_perm(b0, a0, 0x05040100);
+      *reinterpret_cast<int*>(dst + DQ8_VP) =
+          __builtin_amdgcn_perm(b0, a0, 0x07060302);
+      *reinterpret_cast<int*>(dst + 2 * DQ8_VP) =
+          __builtin_amdgcn_perm(b1, a1, 0x05040100);
+      *reinterpret_cast<int*>(dst + 3 * DQ8_VP) =
+          __builtin_amdgcn_perm(b1, a1, 0x07060302);
+    }
+    dq8_load_v<DTILES>(vr, vp, kv0 + 128, end, lane);
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int t = 0; t < DTILES; ++t) {
+      const char* vrow = vt + (16 * t + n) * DQ8_VP + 4 * g;
+      const bf16x8 va =
+          codes_to_bf16(*reinterpret_cast<const int*>(vrow),
+                        *reinterpret_cast<const int*>(vrow + 16));
+      acc[t] *= alpha;
+      acc[t] = mfma_bf16(va, pb, acc[t]);
     }
   }
+
+  dec_split_merge<DTILES>(smem, acc, m_run, l_run, o, ws,
+                          int64_t(b) * H + h0, grp, split, nsplit);
 }
 
 // One wave per (b, h): m* over the splits, then l and acc rescaled and summed
@@ -1666,6 +1934,25 @@ void launch_attn_decode_split(const bf16_t* q, const bf16_t* kc,
   for_head_dim<false>(hd, [&](auto dt) {
     attn_decode_split_k<dt()><<<grid, 256, 0, s>>>(
         q, kc, vc, o, ws, H, grp, Lmax, kvlen, len_p, cb, ch, chunk, scale);
+    if (nsplit > 1)
+      attn_decode_combine_k<dt()><<<(B * H + 3) / 4, 256, 0, s>>>(ws, o, B * H,
+                                                                  nsplit);
+  });
+}
+
+void launch_attn_decode_split_q8(const bf16_t* q, const signed char* kc,
+                                 const signed char* vc, const float* k_scale,
+                                 const float* v_scale, bf16_t* o, float* ws,
+                                 int B, int H, int grp, int Lmax, int Lp,
+                                 int kvlen, const int* len_p, int hd,
+                                 float scale, int nsplit, hipStream_t s) {
+  const dim3 grid(nsplit, H / grp, B);
+  const int chunk = dta_decode_split_chunk(Lmax, nsplit);
+  for_head_dim<false>(hd, [&](auto dt) {
+    attn_decode_split_q8_k<dt()><<<grid, 256, 0, s>>>(
+        q, reinterpret_cast<const char*>(kc),
+        reinterpret_cast<const char*>(vc), k_scale, v_scale, o, ws, H, grp,
+        Lmax, Lp, kvlen, len_p, chunk, scale);
     if (nsplit > 1)
       attn_decode_combine_k<dt()><<<(B * H + 3) / 4, 256, 0, s>>>(ws, o, B * H,
                                                                   nsplit);

@@ -1740,6 +1740,110 @@ Tensor attn_decode_split(Tensor q, Tensor kc, Tensor vc, int64_t kv_len,
   return o;
 }
 
+// ---- int8 KV cache (m.kv_q8) ------------------------------------------------
+// codes int8 [B,Hk,Lmax,D] contiguous, scales fp32 [B,Hk,Lp] contiguous with
+// Lp >= dta_kv_q8_scale_len(Lmax), Lp % 4 == 0; D 64 or 128.
+static void check_kv_q8_cache(const Tensor& kc, const Tensor& vc,
+                              const Tensor& ks, const Tensor& vs) {
+  TORCH_CHECK(kc.is_cuda() && vc.is_cuda() && ks.is_cuda() && vs.is_cuda(),
+              "kv_q8: caches and scales must be GPU tensors");
+  TORCH_CHECK(kc.scalar_type() == torch::kInt8 &&
+                  vc.scalar_type() == torch::kInt8,
+              "kv_q8: code caches must be int8");
+  TORCH_CHECK(ks.scalar_type() == torch::kFloat32 &&
+                  vs.scalar_type() == torch::kFloat32,
+              "kv_q8: scales must be fp32");
+  TORCH_CHECK(kc.dim() == 4 && kc.is_contiguous() && vc.is_contiguous() &&
+                  vc.sizes() == kc.sizes(),
+              "kv_q8: code caches must be contiguous [B,Hk,Lmax,D]");
+  TORCH_CHECK(kc.size(3) == 64 || kc.size(3) == 128,
+              "kv_q8: head dim must be 64/128");
+  TORCH_CHECK(ks.dim() == 3 && ks.is_contiguous() && vs.is_contiguous() &&
+                  vs.sizes() == ks.sizes() && ks.size(0) == kc.size(0) &&
+                  ks.size(1) == kc.size(1) && ks.size(2) % 4 == 0 &&
+                  ks.size(2) >= dta_kv_q8_scale_len(kc.size(2)),
+              "kv_q8: scales must be contiguous [B,Hk,Lp], Lp % 4 == 0, "
+              "Lp >= Lmax rounded up to 32");
+  TORCH_CHECK(kc.size(2) >= 1 && kc.size(2) < (int64_t(1) << 30),
+              "kv_q8: cache capacity");
+}
+
+// k_new / v_new [B,S,Hk,D] bf16 views (D contiguous; slices of a packed qkv
+// or transposed rope outputs) quantised into rows pos .. pos + S - 1. pos_dev:
+// the int32 device counter (S == 1 decode), or empty for the host's pos.
+void kv_append_q8(Tensor kn, Tensor vn, Tensor kc, Tensor vc, Tensor ks,
+                  Tensor vs, Tensor pos_dev, int64_t pos) {
+  check_kv_q8_cache(kc, vc, ks, vs);
+  const int64_t B = kc.size(0), Hk = kc.size(1), Lmax = kc.size(2),
+                D = kc.size(3);
+  KvAppendQ8Args a{};
+  for (const Tensor* t : {&kn, &vn}) {
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == torch::kBFloat16 &&
+                    t->dim() == 4 && t->size(0) == B && t->size(2) == Hk &&
+                    t->size(3) == D && t->sizes() == kn.sizes(),
+                "kv_q8.append: k_new, v_new must be bf16 [B,S,Hk,D]");
+    TORCH_CHECK(t->stride(3) == 1 && t->stride(0) % 8 == 0 &&
+                    t->stride(1) % 8 == 0 && t->stride(2) % 8 == 0 &&
+                    reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0,
+                "kv_q8.append: rows must be contiguous and 16 B aligned");
+  }
+  const int64_t S = kn.size(1);
+  TORCH_CHECK(S >= 1 && B * S * Hk < (int64_t(1) << 30), "kv_q8.append: S");
+  if (pos_dev.numel()) {
+    TORCH_CHECK(pos_dev.scalar_type() == torch::kInt32 && pos_dev.is_cuda(),
+                "kv_q8.append: pos must be an int32 GPU scalar");
+    a.pos_p = pos_dev.data_ptr<int>();
+  } else {
+    TORCH_CHECK(pos >= 0 && pos + S <= Lmax, "kv_q8.append: ", pos, " + ", S,
+                " rows do not fit a cache of ", Lmax);
+  }
+  a.kn = bfp(kn); a.vn = bfp(vn);
+  a.k_sb = kn.stride(0); a.k_ss = kn.stride(1); a.k_sh = kn.stride(2);
+  a.v_sb = vn.stride(0); a.v_ss = vn.stride(1); a.v_sh = vn.stride(2);
+  a.kc = kc.data_ptr<int8_t>(); a.vc = vc.data_ptr<int8_t>();
+  a.k_scale = ks.data_ptr<float>(); a.v_scale = vs.data_ptr<float>();
+  a.pos_h = int(pos); a.B = int(B); a.S = int(S); a.Hk = int(Hk);
+  a.D = int(D); a.Lmax = int(Lmax); a.Lp = int(ks.size(2));
+  launch_kv_append_q8(a, stream());
+}
+
+// attn_decode_split_q8_k (+ attn_decode_combine_k): attn_decode_split's
+// operands with int8 code caches and their scales.
+Tensor attn_decode_split_q8(Tensor q, Tensor kc, Tensor vc, Tensor ks,
+                            Tensor vs, int64_t kv_len, double scale,
+                            Tensor len_dev, int64_t nsplit) {
+  check_bf16(q, "q");
+  check_kv_q8_cache(kc, vc, ks, vs);
+  TORCH_CHECK(q.dim() == 3 && q.is_contiguous(), "q must be contiguous [B,H,D]");
+  const int B = int(q.size(0)), H = int(q.size(1)), hd = int(q.size(2));
+  const int Hk = int(kc.size(1));
+  TORCH_CHECK(kc.size(0) == B && kc.size(3) == hd && H % Hk == 0 &&
+                  kv_len >= 0 && kv_len <= kc.size(2),
+              "kv_q8.attn: bad cache geometry");
+  const int grp = H / Hk;
+  TORCH_CHECK(1 <= grp && grp <= 16, "kv_q8.attn: 1 <= H / Hk <= 16");
+  TORCH_CHECK(nsplit >= 1 && nsplit <= 1024, "kv_q8.attn: 1 <= nsplit <= 1024");
+  TORCH_CHECK(B <= 65535 && Hk <= 65535, "kv_q8.attn: grid limits");
+  const int* lp = nullptr;
+  if (len_dev.numel()) {
+    TORCH_CHECK(len_dev.scalar_type() == torch::kInt32 && len_dev.is_cuda(),
+                "len_dev must be an int32 GPU scalar");
+    lp = len_dev.data_ptr<int>();
+  }
+  auto o = torch::empty_like(q);
+  Tensor ws;
+  if (nsplit > 1)
+    ws = torch::empty({B, H, nsplit, dta_decode_split_row(hd)},
+                      q.options().dtype(torch::kFloat32));
+  launch_attn_decode_split_q8(
+      bfp(q), kc.data_ptr<int8_t>(), vc.data_ptr<int8_t>(),
+      ks.data_ptr<float>(), vs.data_ptr<float>(), bfp_mut(o),
+      nsplit > 1 ? ws.data_ptr<float>() : nullptr, B, H, grp, int(kc.size(2)),
+      int(ks.size(2)), int(kv_len), lp, hd, float(scale), int(nsplit),
+      stream());
+  return o;
+}
+
 // ---- mfma self-test --------------------------------------------------------
 Tensor mfma_selftest_16(Tensor A, Tensor B) {
   check_bf16(A, "A"); check_bf16(B, "B");
@@ -1885,6 +1989,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   // Accuracy tests: tests/test_decode_split_gpu.py.
   py::module_ ds = m.def_submodule("decode_split", "split-KV decode attention");
   ds.def("attn", &attn_decode_split);
-  m.def("mfma_selftest_16", &mfma_selftest_16);
+  // int8 KV cache: quantising append and the split route on codes
+  // (m.kv_q8.append / m.kv_q8.attn). Tests: tests/test_kv_q8_gpu.py.
+  py::module_ kq = m.def_submodule("kv_q8", "int8 KV cache");
+  kq.def("append", &kv_append_q8);
+  kq.def("attn", &attn_decode_split_q8);  m.def("mfma_selftest_16", &mfma_selftest_16);
   m.def("mfma_selftest_32", &mfma_selftest_32);
 }

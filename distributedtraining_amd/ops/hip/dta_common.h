@@ -38,6 +38,18 @@ DEV bf16x8 as_bf16x8(s16x8 v) {
   u.s = v;
   return u.b;
 }
+// 8 int8 codes (two dwords, lowest byte first) -> one MFMA operand; exact,
+// |code| <= 127 fits bf16's significand (w8_gemv.hip, the int8 KV cache)
+DEV bf16x8 codes_to_bf16(int lo, int hi) {
+  bf16x8 r;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    r[e] = static_cast<__bf16>(float(static_cast<signed char>(lo >> (8 * e))));
+    r[4 + e] =
+        static_cast<__bf16>(float(static_cast<signed char>(hi >> (8 * e))));
+  }
+  return r;
+}
 // D[16,16] = A[16,32] x B[32,16] + C; lane layouts: attention.hip header
 DEV f32x4 mfma_bf16(bf16x8 a, bf16x8 b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);

@@ -483,6 +483,24 @@ void launch_kv_append(const bf16_t* kn, const bf16_t* vn, int64_t knb,
                       bf16_t* kc, bf16_t* vc, const int* pos_p, int B,
                       int Hk, int D, int64_t cb, int64_t ch, hipStream_t s);
 void launch_i32_inc(int* p, hipStream_t s);
+// Int8 KV cache (docs/serving.md): codes int8 [B,Hk,Lmax,D] and one fp32
+// scale per (token, KV head) row in [B,Hk,Lp], Lp >= dta_kv_q8_scale_len(Lmax):
+// the decode kernel loads the scales of a whole 32-key tile as 16 B vectors,
+// so a scale row is padded to the tile and rows stay 16 B aligned.
+inline int64_t dta_kv_q8_scale_len(int64_t Lmax) { return (Lmax + 31) / 32 * 32; }
+// Quantising append of S new rows per (b, kv head) at cache row pos, pos =
+// *pos_p when pos_p is set, pos_h otherwise. kn / vn: [B,S,Hk,D] bf16 views
+// with the element strides given (D contiguous, 16 B aligned rows). Rows at
+// or past Lmax are not written.
+struct KvAppendQ8Args {
+  const bf16_t *kn, *vn;
+  int64_t k_sb, k_ss, k_sh, v_sb, v_ss, v_sh;
+  signed char *kc, *vc;
+  float *k_scale, *v_scale;
+  const int* pos_p;
+  int pos_h, B, S, Hk, D, Lmax, Lp;
+};
+void launch_kv_append_q8(const KvAppendQ8Args& a, hipStream_t s);
 void launch_embedding_bwd(const bf16_t* dy, const int64_t* ids,
                           float* dwte_f32, float* dwpe_f32, int64_t n_tok,
                           int seq_len, int dim, bool has_wpe, hipStream_t s);
@@ -702,6 +720,15 @@ void launch_attn_decode_split(const bf16_t* q, const bf16_t* kc,
                               int H, int grp, int Lmax, int kvlen,
                               const int* len_p, int hd, int64_t cb, int64_t ch,
                               float scale, int nsplit, hipStream_t s);
+// The same route on an int8 cache: kc / vc contiguous int8 [B,Hk,Lmax,hd],
+// k_scale / v_scale contiguous fp32 [B,Hk,Lp], Lp >= dta_kv_q8_scale_len(Lmax)
+// and Lp % 4 == 0. Same splits, workspace and combine kernel.
+void launch_attn_decode_split_q8(const bf16_t* q, const signed char* kc,
+                                 const signed char* vc, const float* k_scale,
+                                 const float* v_scale, bf16_t* o, float* ws,
+                                 int B, int H, int grp, int Lmax, int Lp,
+                                 int kvlen, const int* len_p, int hd,
+                                 float scale, int nsplit, hipStream_t s);
 
 // ---- mfma layout self-test ------------------------------------------------
 // D[32,32] = A[32,16] x B[16,32] and D[16,16] = A[16,32] x B[32,16]

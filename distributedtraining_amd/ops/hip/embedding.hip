@@ -154,7 +154,76 @@ __global__ void kv_append_k(const ushort* __restrict__ kn,
 
 __global__ void i32_inc_k(int* p) { ++(*p); }
 
+// Quantising KV-cache append (int8 cache, docs/serving.md): the S new key
+// and value rows of every (b, kv head) go into rows pos .. pos + S - 1 of the
+// int8 code caches [B,Hk,Lmax,D] and their fp32 scales into [B,Hk,Lp], pos
+// = *pos_p (graph-replayed decode) or the host's pos_h (prefill).
+//   * one wave per (row, K or V); lanes < D/8 load 16 B (8 bf16) of the row
+//     through the source's own batch / token / head strides, so slices of a
+//     packed qkv projection and transposed rope outputs are read in place;
+//   * amax by wave reduction (the idle lanes hold 0), scale = amax / 127
+//     (1 for a zero row), code = clamp(rint(x / scale), -127, 127): an IEEE
+//     fp32 divide and round-half-even, equal to ops.kv_quantize bit for bit;
+//   * a lane stores its 8 codes as one 8 B store, lane 0 stores the scale.
+// No atomics, every byte written once, every branch wave-uniform up to the
+// lane < D/8 predicate: capturable and bit-repeatable.
+struct KvQ8Src { const ushort* p; int64_t sb, ss, sh; };   // strides: elements
+__global__ __launch_bounds__(256)
+void kv_append_q8_k(KvQ8Src ks, KvQ8Src vs, signed char* __restrict__ kc,
+                    signed char* __restrict__ vc, float* __restrict__ ksc,
+                    float* __restrict__ vsc, const int* __restrict__ pos_p,
+                    int pos_h, int B, int S, int Hk, int D, int Lmax, int Lp) {
+  const int lane = threadIdx.x & 63;
+  const int64_t w = int64_t(blockIdx.x) * 4 + (threadIdx.x >> 6);
+  const int64_t rows = int64_t(B) * S * Hk;
+  if (w >= 2 * rows) return;                    // wave-uniform
+  const bool is_v = w >= rows;
+  const int64_t r = is_v ? w - rows : w;        // (b, s, h)
+  const int h = int(r % Hk), s = int((r / Hk) % S), b = int(r / (int64_t(Hk) * S));
+  const int row = (pos_p ? *pos_p : pos_h) + s;
+  if (row < 0 || row >= Lmax) return;           // never past the cache
+  const KvQ8Src src = is_v ? vs : ks;
+  const bool own = lane < D / 8;
+  float x[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) x[j] = 0.f;
+  if (own) {
+    const s16x8 v = *reinterpret_cast<const s16x8*>(
+        src.p + b * src.sb + s * src.ss + h * src.sh + 8 * lane);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) x[j] = bf2f(ushort(v[j]));
+  }
+  float amax = 0.f;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) amax = fmaxf(amax, fabsf(x[j]));
+  amax = wave_max(amax);
+  const float scale = amax == 0.f ? 1.0f : amax / 127.0f;
+  const int64_t bh = int64_t(b) * Hk + h;
+  if (own) {
+    int lo = 0, hi = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int q0 = int(fminf(fmaxf(rintf(x[j] / scale), -127.f), 127.f));
+      const int q1 = int(fminf(fmaxf(rintf(x[4 + j] / scale), -127.f), 127.f));
+      lo |= (q0 & 0xff) << (8 * j);
+      hi |= (q1 & 0xff) << (8 * j);
+    }
+    typedef __attribute__((ext_vector_type(2))) int i32x2;
+    *reinterpret_cast<i32x2*>((is_v ? vc : kc) + (bh * Lmax + row) * D +
+                              8 * lane) = i32x2{lo, hi};
+  }
+  if (lane == 0) (is_v ? vsc : ksc)[bh * Lp + row] = scale;
+}
+
 }  // namespace
+
+void launch_kv_append_q8(const KvAppendQ8Args& a, hipStream_t s) {
+  const int64_t waves = 2 * int64_t(a.B) * a.S * a.Hk;
+  kv_append_q8_k<<<unsigned((waves + 3) / 4), 256, 0, s>>>(
+      KvQ8Src{a.kn, a.k_sb, a.k_ss, a.k_sh},
+      KvQ8Src{a.vn, a.v_sb, a.v_ss, a.v_sh}, a.kc, a.vc, a.k_scale, a.v_scale,
+      a.pos_p, a.pos_h, a.B, a.S, a.Hk, a.D, a.Lmax, a.Lp);
+}
 
 void launch_kv_append(const bf16_t* kn, const bf16_t* vn, int64_t knb,
                       bf16_t* kc, bf16_t* vc, const int* pos_p, int B,

@@ -64,18 +64,6 @@ constexpr int W8_DEPTH = 4;               // groups in flight per lane
 static_assert((W8_STAGE / DTA_W8_GROUP) % W8_DEPTH == 0,
               "a stage holds whole turns of the register ring");
 
-// 8 int8 codes (two dwords of the lane's 16 B) -> one MFMA A fragment
-DEV bf16x8 codes_to_bf16(int lo, int hi) {
-  bf16x8 r;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    r[e] = static_cast<__bf16>(float(static_cast<signed char>(lo >> (8 * e))));
-    r[4 + e] =
-        static_cast<__bf16>(float(static_cast<signed char>(hi >> (8 * e))));
-  }
-  return r;
-}
-
 // The scale FMAs and the bias add stay scalar instructions: the packed
 // two-lane fp32 forms are switched off for these kernels.
 template <bool SPLIT>

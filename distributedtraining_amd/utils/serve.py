@@ -37,7 +37,11 @@ def _cached_decode(model, device) -> bool:
 
 class InferenceServer:
     def __init__(self, model, device, host: str = "127.0.0.1",
-                 port: int = 0, max_new_tokens_cap: int = 256):
+                 port: int = 0, max_new_tokens_cap: int = 256,
+                 kv_cache: str = "bf16"):
+        if kv_cache not in ("bf16", "int8"):
+            raise ValueError(f"kv_cache {kv_cache!r} (bf16 or int8)")
+        self.kv_cache = kv_cache    # KV-cache format of every generation
         self.model = model.eval()
         self.device = device
         self.cap = max_new_tokens_cap
@@ -104,7 +108,8 @@ class InferenceServer:
                            eos_token_id=None if eos is None else int(eos),
                            use_cache=_cached_decode(self.model,
                                                     self.device),
-                           seed=None if seed is None else int(seed))
+                           seed=None if seed is None else int(seed),
+                           kv_cache=self.kv_cache)
         self.served += 1
         return {"ids": out.tolist()}
 
