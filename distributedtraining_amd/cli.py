@@ -88,6 +88,10 @@ def main(argv=None) -> int:
                           "one fp32 scale per (token, KV head) row "
                           "(ops.kv_quantize); about half the cache bytes, "
                           "changes the numbers the model produces")
+    top.add_argument("--serve-prefill-chunk", type=int, default=0,
+                     help="serve: prefill prompts longer than N tokens in "
+                          "pieces of N (ops.extend_attention), bounding "
+                          "prompt activation memory; 0 = one pass")
     top.add_argument("--src", default=None,
                      help="convert: HF checkpoint directory "
                           "(save_pretrained layout: config.json + "
@@ -169,7 +173,8 @@ def main(argv=None) -> int:
                   f"{q['kept']} kept, {q['bytes_before']} -> "
                   f"{q['bytes_after']} bytes")
         srv = InferenceServer(model, device, port=ns.port,
-                              kv_cache=ns.serve_kv)
+                              kv_cache=ns.serve_kv,
+                              prefill_chunk=ns.serve_prefill_chunk)
         srv.start()
         print(f"inference server on :{srv.port} (POST /generate)")
         try:

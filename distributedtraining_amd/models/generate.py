@@ -91,7 +91,8 @@ def generate(model, input_ids: torch.Tensor, max_new_tokens: int,
              generator: Optional[torch.Generator] = None,
              use_cache: bool = False,
              seed: Optional[int] = None,
-             kv_cache: str = "bf16") -> torch.Tensor:
+             kv_cache: str = "bf16",
+             prefill_chunk: int = 0) -> torch.Tensor:
     """Extend ``input_ids`` [B, S] by up to ``max_new_tokens``.
 
     temperature 0 = greedy; top_k > 0 restricts sampling to the k highest
@@ -110,13 +111,25 @@ def generate(model, input_ids: torch.Tensor, max_new_tokens: int,
     cache (``KVCache(kv_dtype=)``). int8 halves the cache and the decode
     attention traffic and changes the numbers from the second new token on;
     prefill attends the freshly computed bf16 K and V either way.
+
+    ``prefill_chunk`` (with ``use_cache``): 0 < prefill_chunk < S feeds the
+    prompt to ``model.prefill`` in pieces of that many tokens, each attending
+    the cache filled so far (ops.extend_attention), so prompt activations are
+    bounded by the piece and not by S. 0: one pass. The GPU kernel has no
+    int8-cache form, so chunking an int8 cache there raises.
     """
     if kv_cache not in ("bf16", "int8"):
         raise ValueError(f"generate: kv_cache {kv_cache!r} (bf16 or int8)")
+    if prefill_chunk < 0:
+        raise ValueError(f"generate: prefill_chunk {prefill_chunk}")
+    if (0 < prefill_chunk < input_ids.shape[1] and kv_cache == "int8"
+            and use_cache and input_ids.is_cuda):
+        raise ValueError("generate: chunked prefill has no int8-cache kernel "
+                         "on the GPU (kv_cache='bf16', or prefill_chunk=0)")
     if seed is not None:
         return _generate_seeded(model, input_ids, max_new_tokens, temperature,
                                 top_k, top_p, eos_token_id, use_cache,
-                                int(seed), kv_cache)
+                                int(seed), kv_cache, prefill_chunk)
     model_was_training = model.training
     model.eval()
     n_pos = getattr(model, "cfg").n_positions
@@ -127,7 +140,7 @@ def generate(model, input_ids: torch.Tensor, max_new_tokens: int,
             total = min(ids.shape[1] + max_new_tokens, n_pos)
             cache = model.new_cache(ids.shape[0], total, ids.device,
                                     graphable=ids.is_cuda, kv_dtype=kv_cache)
-            logits = model.prefill(ids, cache).float()
+            logits = _prefill(model, ids, cache, prefill_chunk).float()
             dec = None
             for _ in range(max_new_tokens):
                 nxt = _sample(logits, temperature, top_k, generator,
@@ -169,11 +182,22 @@ def generate(model, input_ids: torch.Tensor, max_new_tokens: int,
     return ids
 
 
+def _prefill(model, ids, cache, chunk):
+    """``model.prefill`` of the prompt, in pieces of ``chunk`` tokens when
+    0 < chunk < S; the logits are those of the last piece."""
+    if not 0 < chunk < ids.shape[1]:
+        return model.prefill(ids, cache)
+    for s0 in range(0, ids.shape[1], chunk):
+        logits = model.prefill(ids[:, s0:s0 + chunk], cache)
+    return logits
+
+
 _POLL = 16     # tokens between two host looks at ``done`` (seeded path)
 
 
 def _generate_seeded(model, input_ids, max_new_tokens, temperature, top_k,
-                     top_p, eos, use_cache, seed, kv_cache="bf16"):
+                     top_p, eos, use_cache, seed, kv_cache="bf16",
+                     prefill_chunk=0):
     from .. import ops
     from ..ops.backend import require_ext
     model_was_training = model.training
@@ -220,7 +244,8 @@ def _generate_seeded(model, input_ids, max_new_tokens, temperature, top_k,
                    pos=cache.pos_dev if cache.pos_dev is not None
                    else cache.len)
 
-        sample_at_cache_pos(model.prefill(input_ids, cache), tok)
+        sample_at_cache_pos(_prefill(model, input_ids, cache, prefill_chunk),
+                            tok)
         dec = None
         for i in range(1, n_new):
             if (i - 1) % _POLL == 0 and eos is not None and bool(done.all()):

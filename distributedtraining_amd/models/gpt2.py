@@ -322,8 +322,9 @@ class KVCache:
 
 def _gpt2_block_attn_cached(blk: GPT2Block, x: torch.Tensor,
                             cache: KVCache, i: int) -> torch.Tensor:
-    """One block with the KV cache: prefill (S>1, causal over itself) or
-    decode (S==1, decode_attention over the cache)."""
+    """One block with the KV cache: prefill (S>1: causal over itself on an
+    empty cache, ops.extend_attention over cache + itself on a filled one)
+    or decode (S==1, decode_attention over the cache)."""
     B, S, E = x.shape
     H = blk.n_head
     D = E // H
@@ -337,8 +338,12 @@ def _gpt2_block_attn_cached(blk: GPT2Block, x: torch.Tensor,
                                  kv_len_dev=cache.pos_dev,
                                  split_kv=cache.split_kv, **cache.scales(i))
         o = o.view(B, 1, E)
+    elif cache.len > 0:   # S > 1 on a filled cache: new rows appended above
+        o = ops.extend_attention(q.view(B, S, H, D).transpose(1, 2),
+                                 cache.k[i], cache.v[i], cache.len,
+                                 split_kv=None, **cache.scales(i))
+        o = o.view(B, S, E)
     else:
-        assert cache.len == 0, "prefill must start an empty cache"
         qv = q.view(B, S, H, D).transpose(1, 2)
         kv_ = k.view(B, S, H, D).transpose(1, 2)
         vv = v.view(B, S, H, D).transpose(1, 2)
@@ -383,7 +388,9 @@ def _gpt2_new_cache(self: "GPT2LM", batch: int, max_len: int, device,
 
 def _gpt2_prefill(self: "GPT2LM", input_ids: torch.Tensor,
                   cache: KVCache) -> torch.Tensor:
-    """Fill the cache with the prompt; returns last-position logits."""
+    """Append the tokens to the cache; returns last-position logits. The
+    cache may already hold tokens (chunked prefill, a second turn): the new
+    ones then attend it through ops.extend_attention."""
     return _gpt2_cached_forward(self, input_ids, cache)
 
 

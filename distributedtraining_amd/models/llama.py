@@ -202,8 +202,9 @@ class LlamaLM(nn.Module):
 
 def _llama_block_attn_cached(blk: LlamaBlock, x: torch.Tensor, cos, sin,
                              cache, i: int, pos=None) -> torch.Tensor:
-    """One Llama block with the KV cache (GQA-aware): prefill (S>1) or
-    decode (S==1 through ops.decode_attention). cos/sin are
+    """One Llama block with the KV cache (GQA-aware): prefill (S>1; on an
+    empty cache ops.causal_attention, on a filled one ops.extend_attention)
+    or decode (S==1 through ops.decode_attention). cos/sin are
     position-offset slices, OR the full tables with ``pos`` a device
     int32 offset (graph-replayable decode)."""
     B, S, E = x.shape
@@ -224,9 +225,12 @@ def _llama_block_attn_cached(blk: LlamaBlock, x: torch.Tensor, cos, sin,
                                  kv_len_dev=cache.pos_dev,
                                  split_kv=cache.split_kv, **cache.scales(i))
         o = o.view(B, 1, E)
-    else:
-        assert cache.len == 0, "prefill must start an empty cache"
+    elif cache.len == 0:
         o = ops.causal_attention(q, k, v).transpose(1, 2).reshape(B, S, E)
+    else:   # S > 1 on a filled cache: the new rows are appended above
+        o = ops.extend_attention(q, cache.k[i], cache.v[i], cache.len,
+                                 split_kv=None, **cache.scales(i))
+        o = o.view(B, S, E)
     x = x + ops.linear(o, blk.o_w)
     h = ops.rms_norm(x, blk.mlp_norm_w, blk.norm_eps)
     h = ops.swiglu(ops.linear(h, blk.gate_w), ops.linear(h, blk.up_w))
@@ -265,6 +269,9 @@ def _llama_new_cache(self: "LlamaLM", batch: int, max_len: int, device,
 
 
 def _llama_prefill(self: "LlamaLM", input_ids: torch.Tensor, cache):
+    """Append the tokens to the cache; returns last-position logits. The
+    cache may already hold tokens (chunked prefill, a second turn): the new
+    ones then attend it through ops.extend_attention."""
     return _llama_cached_forward(self, input_ids, cache)
 
 

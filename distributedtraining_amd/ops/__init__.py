@@ -1103,6 +1103,96 @@ def decode_attention(q: torch.Tensor, k_cache: torch.Tensor,
     return (att @ vf).squeeze(2).to(q.dtype)
 
 
+def extend_split_plan(B: int, H: int, Hk: int, Sq: int, P: int, D: int,
+                      cus: int = 256) -> int:
+    """KV split count of ``extend_attention(split_kv=None)``: Sq new queries
+    per head on a prefix of P cached keys. Two blocks per CU in splits of at
+    least 256 keys, with the kernel's row blocks in the block count:
+    clamp(ceil(2 CUs / (B Hk ceil(Sq grp / 64))), 1, (P + Sq) / 256).
+    Written from profiles/r18_extend_attention.md (tools/extend_attn_ab.py,
+    MI355X, batch 1, Llama-3-8B / Qwen2-7B / GPT-2-small heads, Sq 4..512,
+    P 0..8192; the kernel's arms repeat within 0.5 %): the decode rule's
+    shape (one block per CU, splits >= 512 keys) was up to 1.6x behind the
+    best arm there. This rule is a measured arm at every shape of the table:
+    within 8 % of the best arm at head dim 128 for P > 0, except 11 % at
+    (P 2048, Sq 128, Llama heads); 12-16 % behind at P = 0, Sq 512, where one
+    split is best and the models keep ``causal_attention`` anyway; at head
+    dim 64 it is the best arm at P = 2048 and 16-25 % behind at P = 8192,
+    where splits of 512 keys (half the count) win."""
+    grp = H // Hk if Hk > 0 and H % Hk == 0 else 1
+    blocks = B * Hk * -(-Sq * grp // 64)
+    return max(1, min(-(-2 * cus // blocks), (P + Sq) // 256))
+
+
+def extend_attention(q: torch.Tensor, k_cache: torch.Tensor,
+                     v_cache: torch.Tensor, prefix_len: int,
+                     scale: Optional[float] = None,
+                     split_kv: Optional[int] = None,
+                     k_scale: Optional[torch.Tensor] = None,
+                     v_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Sq >= 1 new queries per head against a filled KV cache: chunked
+    prefill, continuing a cache, verifying drafted tokens. ``q`` is a
+    [B,H,Sq,D] view (D contiguous) of the queries at absolute positions
+    prefix_len .. prefix_len + Sq - 1; the caches are [B,Hk,Lmax,D] with rows
+    0 .. prefix_len + Sq - 1 valid (the new K/V rows appended before the
+    call). Query i of head h sees key j of KV head h // (H // Hk) iff
+    j <= prefix_len + i. Returns [B,Sq,H,D] contiguous, which views as the
+    o-projection's [B,Sq,E] input.
+
+    GPU: attn_extend_k (hip/attention.hip) for bf16, D 64 / 128, 1 <= H / Hk
+    <= 16; anything else raises ``ValueError``, there is no other route.
+    ``split_kv`` n >= 1 cuts the key range into n splits merged in a fixed
+    order (few query rows on a long prefix), None asks ``extend_split_plan``.
+    int8 caches (``k_scale`` / ``v_scale``) raise on the GPU: the kernel has
+    no int8 form. CPU: the fp32 composition below, which defines the op
+    (int8 caches as codes * scale). Inference-only (no autograd)."""
+    if q.dim() != 4 or k_cache.dim() != 4:
+        raise ValueError("extend_attention: q [B,H,Sq,D], caches [B,Hk,Lmax,D]")
+    B, H, Sq, D = q.shape
+    Hk, Lmax = k_cache.shape[1], k_cache.shape[2]
+    P = int(prefix_len)
+    if scale is None:
+        scale = 1.0 / math.sqrt(D)
+    q8 = k_scale is not None or v_scale is not None
+    if q8 and (k_scale is None or v_scale is None):
+        raise ValueError("extend_attention: k_scale and v_scale go together")
+    if Hk <= 0 or H % Hk or P < 0 or Sq < 1 or P + Sq > Lmax:
+        raise ValueError(f"extend_attention: H {H}, Hk {Hk}, prefix {P}, "
+                         f"Sq {Sq}, cache capacity {Lmax}")
+    if use_hip(q):
+        if q8 or k_cache.dtype == torch.int8:
+            raise ValueError("extend_attention: no int8-cache kernel on the "
+                             "GPU (feed an int8 cache one token at a time)")
+        if (q.dtype != torch.bfloat16 or k_cache.dtype != torch.bfloat16
+                or D not in (64, 128) or H // Hk > 16):
+            raise ValueError(
+                f"extend_attention: needs bf16, head dim 64 / 128 and 1 <= "
+                f"heads per KV head <= 16, got {q.dtype}, D = {D}, H = {H}, "
+                f"Hk = {Hk}")
+        if split_kv is None:
+            split_kv = extend_split_plan(B, H, Hk, Sq, P, D)
+        if split_kv < 1:
+            raise ValueError(f"extend_attention: split_kv {split_kv}")
+        if q.stride(3) != 1 or any(s % 8 for s in q.stride()[:3]) \
+                or q.data_ptr() % 16:
+            q = q.contiguous()
+        return require_ext().extend.attn(q, k_cache, v_cache, P, scale,
+                                         split_kv)
+    kf = k_cache[:, :, :P + Sq].float()
+    vf = v_cache[:, :, :P + Sq].float()
+    if q8:
+        kf = kf * k_scale[:, :, :P + Sq, None]
+        vf = vf * v_scale[:, :, :P + Sq, None]
+    kf = kf.repeat_interleave(H // Hk, dim=1)
+    vf = vf.repeat_interleave(H // Hk, dim=1)
+    s = (q.float() @ kf.transpose(-1, -2)) * scale           # [B,H,Sq,P+Sq]
+    j = torch.arange(P + Sq, device=q.device)
+    i = torch.arange(Sq, device=q.device)
+    s = s.masked_fill(j[None, :] > P + i[:, None], float("-inf"))
+    o = torch.softmax(s, dim=-1) @ vf
+    return o.transpose(1, 2).contiguous().to(q.dtype)
+
+
 def _kv_q8_contract(H: int, Hk: int, D: int) -> None:
     """The shapes the int8 decode kernel serves; anything else is an error,
     never another route."""

@@ -37,6 +37,10 @@
 //     comments at the kernels and ops.decode_split_plan. The split route
 //     has an int8-cache sibling, attn_decode_split_q8_k (codes + per-row
 //     scales, written by kv_append_q8_k in embedding.hip).
+//   * Sq > 1 new queries on a filled cache (chunked prefill, a second turn,
+//     verifying drafted tokens): attn_extend_k, one block per 64 (position,
+//     head-in-group) rows of a KV head, optional KV splits merged by
+//     attn_decode_combine_k; see the comment at the kernel.
 //   * swapped QK^T: mfma(A=K_tile, B=Q^T) puts a query's scores in lanes
 //     sharing (lane&15) so the softmax row-reduce is two shfl_xor ops;
 //     exp via the single-instruction exp2 path.
@@ -1770,6 +1774,226 @@ void attn_decode_combine_k(const float* __restrict__ ws,
     o[int64_t(bh) * D + 64 * c + lane] = f2bf(acc[c] * inv);
 }
 
+// ---------------- extend: Sq new queries on a filled KV cache --------------
+// Chunked prefill, a second turn, verifying drafted tokens: Sq >= 1 queries
+// per head at absolute positions P .. P + Sq - 1 attend P cached keys plus
+// themselves (query i sees key j iff j <= P + i; the new rows are already
+// appended). Neither attn_fwd_k (queries and keys share one index range) nor
+// the decode kernels (one query) serve this.
+//   * Rows are (position, head-in-group) pairs of ONE KV head, position-major:
+//     r = i * grp + hn, Sq * grp rows. A block is 4 waves x 16 = 64 consecutive
+//     r of (kv head, batch row); grid = (ceil(Sq grp / 64) * nsplit, Hk, B).
+//     The 64 rows lie within ceil(64 / grp) + 1 positions, so the four waves
+//     share one key walk and each K/V tile reaches LDS once per block for the
+//     whole head group: K/V traffic per KV head is 1 / grp of one attn_fwd_k
+//     pass per query head. A block boundary may fall inside a position's head
+//     group (grp 7: 64 rows = 9 positions + 1 head); nothing relies on it not
+//     doing so, position and head are derived per row. Rows >= Sq * grp are
+//     padding: they load row Sq * grp - 1 again and are never stored.
+//   * Scores swapped as in attn_fwd_k: mfma(A = K tile, B = Q^T), Q^T held
+//     as D/32 B-fragments for the whole block, softmax reduce = two shfl_xor.
+//     P.V without moving P, as in attn_decode_split_k: the score tiles in C
+//     layout are the B-fragment, the A-fragment is V^T read as two 8 B LDS
+//     loads, the product is O^T (acc[t][r] = column 16t + 4g + r of query
+//     n), so alpha, l, 1/l are per lane and a lane stores 4 columns at once.
+//   * LDS per block: K row-major 32 x (D + 8) and V^T D x LDS_RP bf16, one
+//     pair: 8.5 + 10 KB at D = 128, 4.5 + 5 KB at D = 64.
+//   * Loads run a tile ahead through registers (D/64 x 16 B of K and of V per
+//     thread): tile t + 1 is requested right after tile t became visible in
+//     LDS and lands during the MFMAs of tile t. Rows are clamped below P + Sq,
+//     so the look-ahead past the last tile re-reads the last row instead of
+//     branching (see attn_decode_split_k).
+//   * The walk of a block: keys [split start, min(split end, P + last
+//     position of the block + 1)), block-uniform. A tile whose last key is
+//     <= P + first position of the block is visible to every row: those run
+//     in the first loop with no compare. Only the tiles crossing the band of
+//     the block's positions (<= 3 for grp >= 1: 64 rows span <= 65 keys) take
+//     the per-row compare `key <= P + i`, which is the whole mask: it implies
+//     key < P + Sq, and splits start and end on tile boundaries.
+//   * nsplit > 1 (few rows, long prefix): split s owns keys [s chunk,
+//     (s + 1) chunk), chunk a multiple of 32; the block writes fp32 (acc, m, l)
+//     per (row, split) in the dta_decode_split_row format and
+//     attn_decode_combine_k merges B * Sq * H rows in split order. A row that
+//     sees no key of its split keeps m = -inf, l = 0, acc = 0 (alpha and p
+//     are guarded, no exp2 of inf - inf) and the combine skips it.
+// Rounding points: P is rounded to bf16 before P.V with the running max
+// after the current tile, l sums the unrounded fp32 p, partials are fp32, o
+// is rounded once.
+template <int DTILES>
+DEV void ext_load_tile(s16x8 (&kr)[DTILES / 4], s16x8 (&vr)[DTILES / 4],
+                       const ushort* kp, const ushort* vp, int kv0, int kvl,
+                       int tid) {
+  constexpr int CPR = 2 * DTILES;       // 16B chunks per row (D/8)
+#pragma unroll
+  for (int c = 0; c < DTILES / 4; ++c) {
+    const int i = tid + 256 * c;
+    const int64_t off =
+        int64_t(clamp_row(kv0 + i / CPR, kvl)) * (16 * DTILES) + (i % CPR) * 8;
+    kr[c] = *reinterpret_cast<const s16x8*>(kp + off);
+    vr[c] = *reinterpret_cast<const s16x8*>(vp + off);
+  }
+}
+// the LDS layouts of stage_tile: K row-major, V transposed
+template <int DTILES>
+DEV void ext_store_tile(ushort* k_rm, ushort* v_t,
+                        const s16x8 (&kr)[DTILES / 4],
+                        const s16x8 (&vr)[DTILES / 4], int tid) {
+  constexpr int CPR = 2 * DTILES;
+#pragma unroll
+  for (int c = 0; c < DTILES / 4; ++c) {
+    const int i = tid + 256 * c;
+    const int r = i / CPR, c8 = (i % CPR) * 8;
+    *reinterpret_cast<s16x8*>(k_rm + r * LDS_RM_PITCH<DTILES> + c8) = kr[c];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v_t[(c8 + j) * LDS_RP + r] = ushort(vr[c][j]);
+  }
+}
+
+template <int DTILES>  // D = 16*DTILES
+__global__ __launch_bounds__(256)
+void attn_extend_k(const ushort* __restrict__ q,    // [B,H,Sq,D] view
+                   const ushort* __restrict__ kc,   // [B,Hk,Lmax,D]
+                   const ushort* __restrict__ vc,
+                   ushort* __restrict__ o,          // [B,Sq,H,D]
+                   float* __restrict__ ws,  // [B,Sq,H,nsplit,D+4]
+                   ExtGeom geo) {
+  constexpr int D = 16 * DTILES;
+  constexpr int KS = DTILES / 2;            // 32-column steps of a K row
+  __shared__ __attribute__((aligned(16))) ushort k_rm[LDS_RM_SIZE<DTILES>];
+  __shared__ __attribute__((aligned(16))) ushort v_t[LDS_T_SIZE<DTILES>];
+
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int n = lane & 15, g = lane >> 4;
+  const int blk = int(blockIdx.x) / geo.nsplit;
+  const int split = int(blockIdx.x) % geo.nsplit;
+  const int hk = blockIdx.y, b = blockIdx.z;
+  const int grp = geo.grp, P = geo.P;
+  const int R = geo.Sq * grp;               // rows of this KV head
+  const int kvl = P + geo.Sq;               // valid cache rows
+
+  // this lane's query row (column n of the wave's Q^T), clamped into R
+  const int r0 = blk * 64 + wid * 16;
+  const int row = r0 + n;
+  const int rc = min(row, R - 1);
+  const int qi = rc / grp;                  // position within the Sq
+  const int h = hk * grp + (rc - qi * grp);
+  const int qlim = P + qi;                  // last key this row sees
+
+  bf16x8 qb[KS];
+  {
+    const ushort* qp = q + b * geo.q_batch + h * geo.q_head + qi * geo.q_seq;
+#pragma unroll
+    for (int sl = 0; sl < KS; ++sl)
+      qb[sl] = load_frag_row(qp, 0, 0, 32 * sl + 8 * g);
+  }
+  const ushort* kp = kc + b * geo.c_batch + hk * geo.c_head;
+  const ushort* vp = vc + b * geo.c_batch + hk * geo.c_head;
+  const float sc2 = geo.scale * LOG2E;
+
+  // block-uniform walk bounds (blk * 64 < R by the grid)
+  const int i_first = (blk * 64) / grp;
+  const int i_last = min(blk * 64 + 63, R - 1) / grp;
+  const int start = split * geo.chunk;
+  const int end = min(start + geo.chunk, P + i_last + 1);   // may be <= start
+  const int full_end =
+      start + 32 * max(0, (min(end, P + i_first + 1) - start) / 32);
+  // wave-uniform: nothing at or past this key is visible to the wave's rows
+  const int wave_end = r0 < R ? P + min(r0 + 15, R - 1) / grp + 1 : 0;
+
+  f32x4 acc[DTILES];
+#pragma unroll
+  for (int t = 0; t < DTILES; ++t) acc[t] = f32x4{0, 0, 0, 0};
+  float m_run = -INFINITY, l_run = 0.f;   // of query n, in exp2 units
+
+  s16x8 kr[DTILES / 4], vr[DTILES / 4];
+  ext_load_tile<DTILES>(kr, vr, kp, vp, start, kvl, tid);   // clamped
+  auto tile = [&](int kv0, auto masked) {
+    __syncthreads();   // previous tile's LDS reads complete
+    ext_store_tile<DTILES>(k_rm, v_t, kr, vr, tid);
+    __syncthreads();
+    // clamped: in bounds even past the last tile
+    ext_load_tile<DTILES>(kr, vr, kp, vp, kv0 + 32, kvl, tid);
+    if (kv0 >= wave_end) return;   // after the barriers
+    f32x4 p0 = {0, 0, 0, 0}, p1 = {0, 0, 0, 0};
+#pragma unroll
+    for (int sl = 0; sl < KS; ++sl) {
+      const int c0 = 32 * sl + 8 * g;
+      p0 = mfma_bf16(load_frag_rm<DTILES>(k_rm, n, c0), qb[sl], p0);
+      p1 = mfma_bf16(load_frag_rm<DTILES>(k_rm, 16 + n, c0), qb[sl], p1);
+    }
+    float mx = -INFINITY;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      p0[r] *= sc2;
+      p1[r] *= sc2;
+      if constexpr (decltype(masked)::value) {
+        const int k0a = kv0 + 4 * g + r;
+        if (k0a > qlim) p0[r] = -INFINITY;
+        if (k0a + 16 > qlim) p1[r] = -INFINITY;
+      }
+      mx = fmaxf(mx, fmaxf(p0[r], p1[r]));
+    }
+    mx = fmaxf(mx, __shfl_xor(mx, 16));
+    mx = fmaxf(mx, __shfl_xor(mx, 32));
+    const float m_new = fmaxf(m_run, mx);   // -inf: the row saw no key yet
+    const float alpha =
+        (m_run == -INFINITY) ? 0.f : __builtin_exp2f(m_run - m_new);
+    float pf[8];
+    float psum = 0.f;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      pf[r] = __builtin_exp2f(p0[r] - m_new);
+      pf[4 + r] = __builtin_exp2f(p1[r] - m_new);
+      if constexpr (decltype(masked)::value) {   // m_new may be -inf too
+        if (p0[r] == -INFINITY) pf[r] = 0.f;
+        if (p1[r] == -INFINITY) pf[4 + r] = 0.f;
+      }
+      psum += pf[r] + pf[4 + r];
+    }
+    psum += __shfl_xor(psum, 16);
+    psum += __shfl_xor(psum, 32);
+    l_run = l_run * alpha + psum;
+    m_run = m_new;
+    // slot 8g + j of the contraction = key 16*(j >> 2) + 4g + (j & 3)
+    const bf16x8 pb = pack_bf16x8(pf);
+#pragma unroll
+    for (int t = 0; t < DTILES; ++t) {
+      const ushort* vrow = v_t + (16 * t + n) * LDS_RP + 4 * g;
+      const s16x4 lo = *reinterpret_cast<const s16x4*>(vrow);
+      const s16x4 hi = *reinterpret_cast<const s16x4*>(vrow + 16);
+      const bf16x8 va =
+          as_bf16x8(__builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
+      acc[t] *= alpha;
+      acc[t] = mfma_bf16(va, pb, acc[t]);
+    }
+  };
+  int kv0 = start;
+  for (; kv0 < full_end; kv0 += 32) tile(kv0, std::false_type{});
+  for (; kv0 < end; kv0 += 32) tile(kv0, std::true_type{});
+
+  if (row >= R) return;   // padding rows; no barrier follows
+  const int64_t orow = (int64_t(b) * geo.Sq + qi) * geo.H + h;
+  if (geo.nsplit == 1) {
+    const float inv = l_run > 0.f ? 1.0f / l_run : 0.f;
+    ushort* op = o + orow * D + 4 * g;
+#pragma unroll
+    for (int t = 0; t < DTILES; ++t) {
+      s16x4 ob;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) ob[e] = short(f2bf(acc[t][e] * inv));
+      *reinterpret_cast<s16x4*>(op + 16 * t) = ob;
+    }
+  } else {
+    float* wrow = ws + (orow * geo.nsplit + split) * dta_decode_split_row(D);
+#pragma unroll
+    for (int t = 0; t < DTILES; ++t)
+      *reinterpret_cast<f32x4*>(wrow + 16 * t + 4 * g) = acc[t];
+    if (g == 0)
+      *reinterpret_cast<f32x4*>(wrow + D) = f32x4{m_run, l_run, 0.f, 0.f};
+  }
+}
+
 // ---------------- mfma layout probes ----------------
 __global__ void mfma_probe16_k(const ushort* A, const ushort* B, float* D) {
   const int lane = threadIdx.x & 63;
@@ -1937,6 +2161,20 @@ void launch_attn_decode_split(const bf16_t* q, const bf16_t* kc,
     if (nsplit > 1)
       attn_decode_combine_k<dt()><<<(B * H + 3) / 4, 256, 0, s>>>(ws, o, B * H,
                                                                   nsplit);
+  });
+}
+
+void launch_attn_extend(const bf16_t* q, const bf16_t* kc, const bf16_t* vc,
+                        bf16_t* o, float* ws, ExtGeom geo, hipStream_t s) {
+  const int rows = geo.Sq * geo.grp;
+  const dim3 grid(((rows + 63) / 64) * geo.nsplit, geo.H / geo.grp, geo.B);
+  geo.chunk = dta_extend_chunk(geo.P + geo.Sq, geo.nsplit);
+  const int BH = geo.B * geo.Sq * geo.H;
+  for_head_dim<false>(geo.hd, [&](auto dt) {
+    attn_extend_k<dt()><<<grid, 256, 0, s>>>(q, kc, vc, o, ws, geo);
+    if (geo.nsplit > 1)
+      attn_decode_combine_k<dt()><<<(BH + 3) / 4, 256, 0, s>>>(ws, o, BH,
+                                                               geo.nsplit);
   });
 }
 

@@ -1740,6 +1740,54 @@ Tensor attn_decode_split(Tensor q, Tensor kc, Tensor vc, int64_t kv_len,
   return o;
 }
 
+// Extend attention (attn_extend_k [+ attn_decode_combine_k]): q a [B,H,Sq,D]
+// view of Sq new queries at positions prefix .. prefix + Sq - 1, caches
+// [B,Hk,Lmax,D] with those rows already appended; returns o [B,Sq,H,D]. The
+// split workspace is an allocator tensor on the current stream (capturable).
+Tensor attn_extend(Tensor q, Tensor kc, Tensor vc, int64_t prefix,
+                   double scale, int64_t nsplit) {
+  check_bf16(kc, "kcache"); check_bf16(vc, "vcache");
+  TORCH_CHECK(q.is_cuda() && q.scalar_type() == torch::kBFloat16,
+              "q must be a bf16 GPU tensor");   // a view: strides below
+  TORCH_CHECK(q.dim() == 4 && kc.dim() == 4, "q [B,H,Sq,D], cache [B,Hk,L,D]");
+  const int64_t B = q.size(0), H = q.size(1), Sq = q.size(2), hd = q.size(3);
+  const int64_t Hk = kc.size(1), Lmax = kc.size(2);
+  TORCH_CHECK(hd == 64 || hd == 128, "extend attention: head dim 64 or 128");
+  TORCH_CHECK(Hk > 0 && H % Hk == 0 && H / Hk <= 16,
+              "extend attention: 1 <= H / Hk <= 16");
+  TORCH_CHECK(Sq >= 1 && prefix >= 0 && prefix + Sq <= Lmax,
+              "extend attention: prefix + Sq must fit the cache");
+  TORCH_CHECK(kc.is_contiguous() && vc.is_contiguous() && kc.size(0) == B &&
+                  kc.size(3) == hd && vc.sizes() == kc.sizes(),
+              "extend attention needs contiguous [B,Hk,L,D] caches");
+  TORCH_CHECK(q.stride(3) == 1 && q.stride(0) % 8 == 0 &&
+                  q.stride(1) % 8 == 0 && q.stride(2) % 8 == 0 &&
+                  reinterpret_cast<uintptr_t>(q.data_ptr()) % 16 == 0,
+              "extend attention: q rows must be contiguous and 16 B aligned");
+  TORCH_CHECK(nsplit >= 1 && nsplit <= 1024,
+              "extend attention: 1 <= nsplit <= 1024");
+  const int64_t nblk = (Sq * (H / Hk) + 63) / 64;
+  TORCH_CHECK(B <= 65535 && Hk <= 65535 && Lmax < (int64_t(1) << 30) &&
+                  nblk * nsplit < (int64_t(1) << 31) &&
+                  B * Sq * H < (int64_t(1) << 31),
+              "extend attention: grid limits");
+  auto o = torch::empty({B, Sq, H, hd}, q.options());
+  Tensor ws;
+  if (nsplit > 1)
+    ws = torch::empty({B, Sq, H, nsplit, dta_decode_split_row(int(hd))},
+                      q.options().dtype(torch::kFloat32));
+  ExtGeom geo{};
+  geo.B = int(B); geo.H = int(H); geo.grp = int(H / Hk); geo.Sq = int(Sq);
+  geo.P = int(prefix); geo.hd = int(hd); geo.nsplit = int(nsplit);
+  geo.q_batch = q.stride(0); geo.q_head = q.stride(1); geo.q_seq = q.stride(2);
+  geo.c_batch = kc.stride(0); geo.c_head = kc.stride(1);
+  geo.scale = float(scale);
+  launch_attn_extend(bfp(q), bfp(kc), bfp(vc), bfp_mut(o),
+                     nsplit > 1 ? ws.data_ptr<float>() : nullptr, geo,
+                     stream());
+  return o;
+}
+
 // ---- int8 KV cache (m.kv_q8) ------------------------------------------------
 // codes int8 [B,Hk,Lmax,D] contiguous, scales fp32 [B,Hk,Lp] contiguous with
 // Lp >= dta_kv_q8_scale_len(Lmax), Lp % 4 == 0; D 64 or 128.
@@ -1993,6 +2041,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   // (m.kv_q8.append / m.kv_q8.attn). Tests: tests/test_kv_q8_gpu.py.
   py::module_ kq = m.def_submodule("kv_q8", "int8 KV cache");
   kq.def("append", &kv_append_q8);
-  kq.def("attn", &attn_decode_split_q8);  m.def("mfma_selftest_16", &mfma_selftest_16);
+  kq.def("attn", &attn_decode_split_q8);
+  // Sq > 1 queries on a filled cache (m.extend.attn).
+  // Tests: tests/test_extend_attn_gpu.py.
+  py::module_ ex = m.def_submodule("extend", "extend attention");
+  ex.def("attn", &attn_extend);
+  m.def("mfma_selftest_16", &mfma_selftest_16);
   m.def("mfma_selftest_32", &mfma_selftest_32);
 }

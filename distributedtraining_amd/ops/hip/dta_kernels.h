@@ -730,6 +730,29 @@ void launch_attn_decode_split_q8(const bf16_t* q, const signed char* kc,
                                  int kvlen, const int* len_p, int hd,
                                  float scale, int nsplit, hipStream_t s);
 
+// Extend attention (attn_extend_k): Sq >= 1 new queries per head at absolute
+// positions P .. P + Sq - 1 against a cache whose rows 0 .. P + Sq - 1 are
+// valid (the new rows already appended); query i sees key j iff j <= P + i.
+// q is a [B,H,Sq,hd] view (element strides, hd contiguous, 16 B aligned
+// rows), the caches contiguous [B,Hk,Lmax,hd], o contiguous [B,Sq,H,hd].
+// 1 <= grp <= 16, hd 64 or 128, P + Sq <= Lmax.
+struct ExtGeom {
+  int B, H, grp, Sq, P, hd;
+  int nsplit, chunk;            // split s owns keys [s * chunk, (s+1) * chunk)
+  int64_t q_batch, q_head, q_seq;
+  int64_t c_batch, c_head;      // cache strides (row stride = hd)
+  float scale;
+};
+// Keys per split: a multiple of the 32-key tile covering P + Sq in nsplit.
+inline int dta_extend_chunk(int kv, int nsplit) {
+  return 32 * ((kv + 32 * nsplit - 1) / (32 * nsplit));
+}
+// ws: [B, Sq, H, nsplit, dta_decode_split_row(hd)] fp32, unused (may be null)
+// when nsplit == 1; merged by attn_decode_combine_k over B * Sq * H rows.
+// geo.chunk is set by the launcher.
+void launch_attn_extend(const bf16_t* q, const bf16_t* kc, const bf16_t* vc,
+                        bf16_t* o, float* ws, ExtGeom geo, hipStream_t s);
+
 // ---- mfma layout self-test ------------------------------------------------
 // D[32,32] = A[32,16] x B[16,32] and D[16,16] = A[16,32] x B[32,16]
 void launch_mfma_probe_32(const bf16_t* A, const bf16_t* B, float* D,

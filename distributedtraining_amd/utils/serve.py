@@ -38,10 +38,18 @@ def _cached_decode(model, device) -> bool:
 class InferenceServer:
     def __init__(self, model, device, host: str = "127.0.0.1",
                  port: int = 0, max_new_tokens_cap: int = 256,
-                 kv_cache: str = "bf16"):
+                 kv_cache: str = "bf16", prefill_chunk: int = 0):
         if kv_cache not in ("bf16", "int8"):
             raise ValueError(f"kv_cache {kv_cache!r} (bf16 or int8)")
+        if prefill_chunk < 0:
+            raise ValueError(f"prefill_chunk {prefill_chunk}")
+        if (prefill_chunk and kv_cache == "int8"
+                and torch.device(device).type == "cuda"):
+            raise ValueError("chunked prefill has no int8-cache kernel on "
+                             "the GPU (kv_cache='bf16', or prefill_chunk=0)")
         self.kv_cache = kv_cache    # KV-cache format of every generation
+        # prompts longer than this are prefilled in pieces (generate)
+        self.prefill_chunk = prefill_chunk
         self.model = model.eval()
         self.device = device
         self.cap = max_new_tokens_cap
@@ -109,7 +117,8 @@ class InferenceServer:
                            use_cache=_cached_decode(self.model,
                                                     self.device),
                            seed=None if seed is None else int(seed),
-                           kv_cache=self.kv_cache)
+                           kv_cache=self.kv_cache,
+                           prefill_chunk=self.prefill_chunk)
         self.served += 1
         return {"ids": out.tolist()}
 
