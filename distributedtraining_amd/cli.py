@@ -77,10 +77,10 @@ def main(argv=None) -> int:
     top.add_argument("--metrics-dir", default="metrics")
     top.add_argument("--port", type=int, default=8500,
                      help="bootstrap: HTTP port")
-    top.add_argument("--serve-weights", choices=["bf16", "int8"],
+    top.add_argument("--serve-weights", choices=["bf16", "int8", "int4"],
                      default="bf16",
-                     help="serve: int8 stores the projection and head "
-                          "weights as int8 codes + group scales "
+                     help="serve: int8 / int4 store the projection and head "
+                          "weights as 8- / 4-bit codes + group scales "
                           "(models.quantize_for_serving); changes the "
                           "numbers the model produces")
     top.add_argument("--serve-kv", choices=["bf16", "int8"], default="bf16",
@@ -166,10 +166,11 @@ def main(argv=None) -> int:
             fp = _FP(model, device=device)
             fp.load_flat_master(st["flat_master"])
             print("serving the store's current base model")
-        if ns.serve_weights == "int8":
+        if ns.serve_weights != "bf16":
             from .models import quantize_for_serving
-            q = quantize_for_serving(model)
-            print(f"int8 weights: {q['converted']} layers converted, "
+            q = quantize_for_serving(model, weights=ns.serve_weights)
+            print(f"{ns.serve_weights} weights: {q['converted']} layers "
+                  f"converted, "
                   f"{q['kept']} kept, {q['bytes_before']} -> "
                   f"{q['bytes_after']} bytes")
         srv = InferenceServer(model, device, port=ns.port,

@@ -37,10 +37,11 @@ from . import droprng
 from .backend import require_ext, use_hip
 from .sampling import sample_cdf, sample_tokens
 from .w8 import (QuantWeight, dequantize_weight, linear_w8,
-                 quantize_weight_int8)
+                 quantize_weight_int4, quantize_weight_int8)
 
 __all__ = [
-    "QuantWeight", "quantize_weight_int8", "dequantize_weight",
+    "QuantWeight", "quantize_weight_int8", "quantize_weight_int4",
+    "dequantize_weight",
     "layer_norm", "rms_norm", "gelu", "swiglu", "causal_attention",
     "qkv_attention", "linear", "mlp_gelu", "add_layer_norm",
     "add_rms_norm",

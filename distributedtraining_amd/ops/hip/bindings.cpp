@@ -1414,6 +1414,93 @@ Tensor w8_dequant(Tensor codes, Tensor scales, int64_t N) {
   return w;
 }
 
+// ---- int4 weight-only serving GEMM (w4_gemv.hip) ----------------------------
+// The packed operand of both entry points: codes uint8 [Np/16, K/128, 64, 16],
+// scales fp32 [Np/16, K/128, 16], Np = ceil16(N). Returns K.
+int w4_check_packed(const Tensor& codes, const Tensor& scales, int64_t N) {
+  TORCH_CHECK(codes.is_cuda() && scales.is_cuda() &&
+                  codes.device() == scales.device(),
+              "codes and scales must be on one GPU");
+  TORCH_CHECK(codes.scalar_type() == torch::kUInt8 && codes.is_contiguous() &&
+                  codes.dim() == 4 && codes.size(2) == 64 &&
+                  codes.size(3) == 16,
+              "codes must be contiguous uint8 [Np/16, K/128, 64, 16]");
+  const int64_t tiles = codes.size(0), K = codes.size(1) * DTA_W8_GROUP;
+  TORCH_CHECK(N >= 1 && tiles == (N + 15) / 16,
+              "codes hold ceil(N / 16) row tiles");
+  TORCH_CHECK(K >= DTA_W8_GROUP && K < (int64_t(1) << 22) &&
+                  N < (int64_t(1) << 26),
+              "K must be a multiple of 128 (< 2^22), N < 2^26");
+  TORCH_CHECK(scales.scalar_type() == torch::kFloat32 &&
+                  scales.is_contiguous() && scales.dim() == 3 &&
+                  scales.size(0) == tiles &&
+                  scales.size(1) == K / DTA_W8_GROUP && scales.size(2) == 16,
+              "scales must be contiguous fp32 [Np/16, K/128, 16]");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(codes.data_ptr()) % 16 == 0 &&
+                  reinterpret_cast<uintptr_t>(scales.data_ptr()) % 16 == 0,
+              "codes and scales must be 16-byte aligned");
+  return int(K);
+}
+int64_t w4_nsplit(int64_t N, int64_t K) {
+  return dta_w4_nsplit(
+      N, int(K), at::cuda::getCurrentDeviceProperties()->multiProcessorCount);
+}
+// y [M, N] bf16 = x [M, K] · Wq^T (+ bias), 1 <= M <= 16. nsplit 0: the
+// automatic K split. Capturable: the partials come from the allocator, no
+// host sync.
+Tensor w4_gemv(Tensor x, Tensor codes, Tensor scales, OptTensor bias,
+               int64_t N, int64_t nsplit) {
+  const int K = w4_check_packed(codes, scales, N);
+  check_bf16(x, "x");
+  TORCH_CHECK(x.device() == codes.device(), "x must be on the weight's GPU");
+  TORCH_CHECK(x.dim() == 2 && x.size(1) == K, "x must be [M, K]");
+  const int64_t M = x.size(0);
+  TORCH_CHECK(M >= 1 && M <= DTA_W8_MAX_M, "w4_gemv is for 1 <= M <= 16");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0,
+              "x must be 16-byte aligned");
+  const bf16_t* bp = nullptr;
+  if (bias.has_value() && bias->defined() && bias->numel()) {
+    check_bf16(*bias, "bias");
+    TORCH_CHECK(bias->numel() == N && bias->device() == x.device(),
+                "bias must be bf16 [N] on x's device");
+    bp = bfp(*bias);
+  }
+  const int groups = K / DTA_W8_GROUP;
+  TORCH_CHECK(nsplit >= 0 && nsplit <= groups,
+              "nsplit must lie in [0, K / 128]");
+  const int ns = nsplit == 0 ? int(w4_nsplit(N, K)) : int(nsplit);
+  auto y = torch::empty({M, N}, x.options());
+  Tensor part;
+  if (ns > 1)
+    part = torch::empty({int64_t(ns), M, N},
+                        x.options().dtype(torch::kFloat32));
+  W8GemvArgs a;
+  a.x = bfp(x);
+  a.codes = codes.data_ptr<uint8_t>();
+  a.scales = scales.data_ptr<float>();
+  a.bias = bp;
+  a.y = bfp_mut(y);
+  a.part = ns > 1 ? part.data_ptr<float>() : nullptr;
+  a.M = int(M); a.N = int(N); a.K = K; a.nsplit = ns;
+  launch_w4_gemv(a, stream());
+  const hipError_t err = hipGetLastError();
+  TORCH_CHECK(err == hipSuccess, "w4_gemv launch failed: ",
+              hipGetErrorString(err));
+  return y;
+}
+// dense bf16 [N, K] = bf16(float(u - 8) * scale)
+Tensor w4_dequant(Tensor codes, Tensor scales, int64_t N) {
+  const int K = w4_check_packed(codes, scales, N);
+  auto w = torch::empty({N, int64_t(K)},
+                        codes.options().dtype(torch::kBFloat16));
+  launch_w4_dequant(codes.data_ptr<uint8_t>(), scales.data_ptr<float>(),
+                    bfp_mut(w), int(N), K, stream());
+  const hipError_t err = hipGetLastError();
+  TORCH_CHECK(err == hipSuccess, "w4_dequant launch failed: ",
+              hipGetErrorString(err));
+  return w;
+}
+
 // ---- rope ------------------------------------------------------------------
 Tensor rope_apply(Tensor x, Tensor cos_t, Tensor sin_t, bool backward,
                   const Tensor& pos) {
@@ -1972,6 +2059,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   w8.def("nsplit", &w8_nsplit);
   m.attr("w8_gemv") = w8.attr("gemv");
   m.attr("w8_dequant") = w8.attr("dequant");
+  // w4_gemv.hip: the int4 sibling, registered the same way (m.w4_gemv /
+  // m.w4_dequant). Tests: tests/test_w4_gemv_gpu.py.
+  py::module_ w4 = m.def_submodule("w4", "int4 weight-only serving GEMM");
+  w4.def("gemv", &w4_gemv, py::arg("x"), py::arg("codes"), py::arg("scales"),
+         py::arg("bias"), py::arg("N"), py::arg("nsplit") = 0);
+  w4.def("dequant", &w4_dequant, py::arg("codes"), py::arg("scales"),
+         py::arg("N"));
+  w4.def("nsplit", &w4_nsplit);
+  m.attr("w4_gemv") = w4.attr("gemv");
+  m.attr("w4_dequant") = w4.attr("dequant");
   // trimmed_merge_k: its own submodule as well. CPU definition:
   // ops.trimmed_merge; tests/test_robust_merge_gpu.py holds the kernel to it
   // bit for bit.

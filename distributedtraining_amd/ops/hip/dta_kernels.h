@@ -539,7 +539,7 @@ inline int dta_w8_nsplit(int64_t N, int K, int cus) {
 }
 struct W8GemvArgs {
   const bf16_t* x;
-  const signed char* codes;
+  const void* codes;    // int8 codes (w8) or packed nibbles (w4)
   const float* scales;
   const bf16_t* bias;   // null: none
   bf16_t* y;
@@ -549,6 +549,36 @@ struct W8GemvArgs {
 void launch_w8_gemv(const W8GemvArgs& a, hipStream_t s);
 // w [N,K] bf16 = bf16(float(code) * scale): the M > 16 route (prefill)
 void launch_w8_dequant(const signed char* codes, const float* scales,
+                       bf16_t* w, int N, int K, hipStream_t s);
+// y[e] = bf16(sum of part[i][e] over the nsplit slices in ascending order
+// + bias[e % N]), e over MN = M * N: the fold of both weight-only routes
+void launch_w8_fold(const float* part, const bf16_t* bias, bf16_t* y,
+                    int nsplit, int64_t MN, int N, hipStream_t s);
+
+// ---- int4 weight-only serving GEMM (w4_gemv.hip) ---------------------------
+// The same product on 4-bit codes: Wq[n,k] = float(u - 8) * scale[n, k /
+// DTA_W8_GROUP], u = q + 8 in 1 .. 15. Packed operand, rows padded with the
+// zero code 8 to Np = ceil16(N): codes uint8 [Np/16][K/128][64][16] (lane and
+// nibble order: w4_gemv.hip header), scales fp32 [Np/16][K/128][16]. The
+// argument contract is launch_w8_gemv's (W8GemvArgs, codes = the nibbles).
+constexpr int DTA_W4_RING = 8;      // groups a lane keeps in flight
+// K split: two blocks per CU, but a slice is never shorter than one turn of
+// the register ring (DTA_W4_RING groups = 1024 columns, one LDS stage): a
+// short slice is all ramp-up, the loss profiles/r14_w8_gemv.md records for
+// single-group int8 slices at the deep-K, few-row shapes. K below two turns
+// is not split; enough row blocks alone take one slice.
+inline int dta_w4_nsplit(int64_t N, int K, int cus) {
+  const int64_t rb = (N + DTA_W8_ROWS - 1) / DTA_W8_ROWS;
+  const int64_t groups = K / DTA_W8_GROUP;
+  int64_t ns = (2 * int64_t(cus) + rb - 1) / (rb > 0 ? rb : 1);
+  if (ns > groups / DTA_W4_RING) ns = groups / DTA_W4_RING;
+  if (ns <= 1) return 1;
+  const int64_t per = (groups + ns - 1) / ns;   // >= DTA_W4_RING
+  return int((groups + per - 1) / per);         // no empty slice
+}
+void launch_w4_gemv(const W8GemvArgs& a, hipStream_t s);
+// w [N,K] bf16 = bf16(float(u - 8) * scale): the M > 16 route (prefill)
+void launch_w4_dequant(const unsigned char* codes, const float* scales,
                        bf16_t* w, int N, int K, hipStream_t s);
 
 // ---- token sampler (sample.hip) --------------------------------------------

@@ -261,7 +261,7 @@ void launch_w8_gemv(const W8GemvArgs& a, hipStream_t s) {
   const int per = (groups + a.nsplit - 1) / a.nsplit;
   const dim3 grid(unsigned((a.N + DTA_W8_ROWS - 1) / DTA_W8_ROWS),
                   unsigned(a.nsplit));
-  const char* codes = reinterpret_cast<const char*>(a.codes);
+  const char* codes = static_cast<const char*>(a.codes);
   if (a.nsplit == 1) {
     w8_gemv_k<false><<<grid, W8_THREADS, 0, s>>>(
         a.x, codes, a.scales, a.bias, a.y, nullptr, a.M, a.N, a.K,
@@ -271,9 +271,13 @@ void launch_w8_gemv(const W8GemvArgs& a, hipStream_t s) {
   w8_gemv_k<true><<<grid, W8_THREADS, 0, s>>>(
       a.x, codes, a.scales, nullptr, nullptr, a.part, a.M, a.N, a.K,
       per * DTA_W8_GROUP);
-  const int64_t MN = int64_t(a.M) * a.N;
-  w8_fold_k<<<elementwise_grid(MN, 256, 1), 256, 0, s>>>(
-      a.part, a.bias, a.y, a.nsplit, MN, a.N);
+  launch_w8_fold(a.part, a.bias, a.y, a.nsplit, int64_t(a.M) * a.N, a.N, s);
+}
+
+void launch_w8_fold(const float* part, const bf16_t* bias, bf16_t* y,
+                    int nsplit, int64_t MN, int N, hipStream_t s) {
+  w8_fold_k<<<elementwise_grid(MN, 256, 1), 256, 0, s>>>(part, bias, y,
+                                                         nsplit, MN, N);
 }
 
 void launch_w8_dequant(const signed char* codes, const float* scales,

@@ -28,6 +28,7 @@ SRC = [
     "distributedtraining_amd/ops/hip/rope.hip",
     "distributedtraining_amd/ops/hip/gemv.hip",
     "distributedtraining_amd/ops/hip/w8_gemv.hip",
+    "distributedtraining_amd/ops/hip/w4_gemv.hip",
     "distributedtraining_amd/ops/hip/sample.hip",
     "distributedtraining_amd/ops/hip/merge.hip",
     "distributedtraining_amd/ops/hip/attention.hip",
